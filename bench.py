@@ -4,16 +4,19 @@ backward + gradient all-reduce + Adam step) on 4096-point S3DIS-like blocks.
 
 Headline (BASELINE.json metric "points/sec fwd+bwd, 4096-pt S3DIS blocks,
 PointNet++/DGCNN @1/2/4/8 GPU"): `value` is PointNet++ SSG, batch 32 per GPU,
-4096 points (configs[1]); the same JSON line carries the DGCNN EdgeConv half of the
-metric (configs[2]: DGCNN-colour k=20, batch 32 per GPU) as `secondary`, timed the
-same way in the same process.  fp32, synthetic blocks resident in HBM before timing.
+4096 points (configs[1]); with `--full` the same JSON line carries the DGCNN EdgeConv
+half of the metric (configs[2]: DGCNN-colour k=20, batch 32 per GPU) as `secondary`, timed
+the same way in the same process.  fp32, synthetic blocks resident in HBM before timing.
 
 Multi-GPU: one process per GPU, data-parallel, RCCL all-reduce of the flat gradient
 buffer, fixed per-GPU batch ("weak" scaling).  `--gpus N` either runs under an
 external launcher (torchrun sets WORLD_SIZE, which must equal N) or, without one,
 spawns the N rank processes itself before touching the GPU.
 
-Also reported on the same JSON line, per workload:
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the headline needs: it sets up
+--model's workload, warms up, times the N steps, writes `--dump-outputs DIR` if asked and prints
+the line.  `--full` adds everything else below: the secondary workload and the other configs,
+the drop-in step, the detail file, and, per workload:
   roofline      -- the dominant HIP kernel (the engine GEMM variant with the largest
                    time in one probed step): its algorithmic flops and bytes per launch
                    over its IN-STEP launch time (HIP events on the stream it runs on,
@@ -75,6 +78,26 @@ def model_input(pts, kind):
 
 def logits_of(out):
     return out[0] if isinstance(out, tuple) else out
+
+
+DUMP_LIMIT = 64 << 20        # bytes of .npy payload per --dump-outputs directory
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT):
+    """Write {name: tensor} as path/<name>.npy in float32 (float64 stays float64).  An array over
+    its equal share of `limit` bytes is cut to a fixed sample of its flattened elements (sorted
+    indices drawn once from numpy's default_rng(0): the same for every run and build)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = limit // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = np.asarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        keep = share // a.itemsize
+        if a.size > keep:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def host_cpu_info():
@@ -324,7 +347,7 @@ def step_roofline(key, npoints, batch, ms, roof=None):
 
 
 # ----------------------------------------------------------------------------- one workload
-def run_workload(key, batch, npoints, args, world, rank, dev):
+def run_workload(key, batch, npoints, args, world, rank, dev, dump_dir=None):
     import torch
     import torch.distributed as dist
     import pcseg
@@ -351,6 +374,7 @@ def run_workload(key, batch, npoints, args, world, rank, dev):
 
     in_bwd = args.prefetch_point == 'backward'
     at_start = args.prefetch_point == 'start'
+    last = {'keep': False}      # --dump-outputs: the last timed step keeps a copy of its logits
 
     def step():
         grads.zero_grad()
@@ -361,7 +385,10 @@ def run_workload(key, batch, npoints, args, world, rank, dev):
             model.prefetch_geometry_in_backward(x)
         if prefetch and at_start:
             model.prefetch_geometry_at_start(x)      # enqueued right after this forward takes its plan
-        loss = pcseg.masked_onehot_cross_entropy(logits_of(model(x)), lab, lengths)
+        logits = logits_of(model(x))
+        if last['keep']:
+            last['logits'] = logits.detach().clone()
+        loss = pcseg.masked_onehot_cross_entropy(logits, lab, lengths)
         if prefetch and not in_bwd and not at_start:
             model.prefetch_geometry(x)
         loss.backward()
@@ -415,8 +442,9 @@ def run_workload(key, batch, npoints, args, world, rank, dev):
     from pcseg import engine as _eng
     w0 = _eng.inflight_wait_s[0] + getattr(opt, 'wait_s', 0.0)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
         cur[0] = time.perf_counter()
+        last['keep'] = bool(dump_dir) and i == args.steps - 1
         loss = step()
         if steplog:
             th.append(time.perf_counter())
@@ -443,6 +471,16 @@ def run_workload(key, batch, npoints, args, world, rank, dev):
         dt = float(t)
     if not torch.isfinite(loss):
         raise RuntimeError(f'{name}: non-finite loss')
+    if dump_dir and rank == 0:
+        # what the last timed step handed its caller: the loss, the gradients it left in the flat
+        # buffer, the parameters after its Adam update and (eager steps) its logits -- written
+        # before the roofline probe runs one more step over them
+        out = {'loss': loss, 'grads': grads.flat, 'params': opt.flat}
+        if 'logits' in last:
+            out['logits'] = last['logits']
+        dump_outputs(dump_dir, out)
+    last.pop('logits', None)
+    last['keep'] = False
     roof = None
     if not args.no_roofline:
         roof = kernel_roofline(eager_step, dev, key, batch, npoints, replay=args.roofline_replay)
@@ -696,12 +734,22 @@ def spawn_ranks(n):
     return max(rcs, key=abs)
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--model', default='pointnetpp', choices=sorted(WORKLOADS))
+    ap.add_argument('--full', action='store_true',
+                    help='beside the headline workload, also run the secondary workload, the other configs, the '
+                         'drop-in step, the roofline probes and the CPU baselines, and write the detail file '
+                         '(each still subject to its own --no-... / none switch); without it only --model\'s '
+                         'workload is set up, warmed up and timed')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step of --model\'s workload computed '
+                         '(loss, logits, flat gradients, flat parameters after the update) as DIR/<name>.npy, '
+                         'float32, at most 64 MB in all; the inputs are seeded, so two builds compare output '
+                         'for output')
     ap.add_argument('--secondary', default='auto', help="second workload on the same line ('auto': dgcnn when "
                                                         "--model is pointnetpp; 'none' to skip)")
     ap.add_argument('--others', default='auto',
@@ -747,7 +795,7 @@ def main():
                          "the printed line names it ('none': not written)")
     ap.add_argument('--check-launch', action='store_true',
                     help='launcher self-test: each rank joins a gloo group, prints its env as JSON, exits (no GPU)')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.cpu_baseline_worker:
         cpu_baseline_worker(args)
         return 0
@@ -771,6 +819,13 @@ def main():
         dist.destroy_process_group()
         return 0
 
+    if not args.full:
+        # the plain run: the headline workload's timed steps and nothing else
+        for flag, v in (('--secondary', args.secondary), ('--others', args.others)):
+            if v not in ('auto', 'none'):
+                raise SystemExit(f'bench.py: {flag} {v} needs --full')
+        args.secondary = args.others = args.detail_out = 'none'
+        args.no_cpu_baseline = args.no_roofline = args.no_drop_in = True
     keys = [args.model]
     sec = args.secondary
     if sec == 'auto':
@@ -804,7 +859,8 @@ def main():
 
     results = {}
     for k in keys + others:
-        results[k] = run_workload(k, *sizes[k], args, world, rank, dev)
+        results[k] = run_workload(k, *sizes[k], args, world, rank, dev,
+                                  dump_dir=args.dump_outputs if k == args.model else None)
         release_cached(dev)     # the model, its closures and plans are gone: hand their blocks back
     if world == 1 and not args.no_drop_in:
         for k in keys + others:

@@ -52,6 +52,47 @@ def test_line_is_compact_last_and_complete(tmp_path, capsys):
     assert rec['detail'] == os.path.relpath(str(det), REPO)
 
 
+def test_plain_record_has_the_contract_keys_and_no_extras():
+    """The line of a run without --full: one workload, no roofline, CPU baseline, drop-in,
+    secondary, other configs or detail file -- and still the contract's keys."""
+    w = {'value': 1.0e7, 'unit': 'points/s', 'ms_per_step': 13.1, 'config': {'workload': 'w', 'model': 'PointNetpp'},
+         'host_enqueue_ms_per_step': 3.0, 'host_runahead_wait_ms_per_step': 0.0, 'roofline': None,
+         'step_roofline': None}
+    args = type('A', (), {'model': 'pointnetpp', 'steps': 7, 'warmup': 2})()
+    full = bench.full_record({'pointnetpp': w}, {}, args, 1, 1, ['pointnetpp'], [])
+    rec = bench.compact_line(full, None)
+    for k, v in (('metric', bench.METRIC), ('value', 1.0e7), ('unit', 'points/s'), ('higher_is_better', True),
+                 ('dtype', 'fp32'), ('ms_per_step', 13.1), ('steps', 7), ('warmup', 2), ('n_gpus', 1)):
+        assert rec[k] == v, k
+    assert rec['roofline'] is None and rec['cpu_baseline'] is None and rec['detail'] is None
+    assert not {'secondary', 'other_configs', 'drop_in'} & set(rec)
+
+
+def test_extra_workloads_need_full():
+    import pytest
+    for flag, v in (('--secondary', 'dgcnn'), ('--others', 'pointnext')):
+        with pytest.raises(SystemExit, match='needs --full'):
+            bench.main(['--gpus', '1', flag, v])
+
+
+def test_dump_outputs_writes_float_npy_within_the_limit(tmp_path):
+    import numpy as np
+    import torch
+    arrays = {'loss': torch.tensor(0.5), 'big': torch.arange(1000, dtype=torch.float32).reshape(10, 100),
+              'ints': torch.arange(6, dtype=torch.int32), 'wide': torch.arange(4, dtype=torch.float64)}
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=4 * 400)     # 400 bytes each: 100 fp32 of `big`
+    got = {n: np.load(tmp_path / 'a' / f'{n}.npy') for n in arrays}
+    assert got['loss'].dtype == np.float32 and got['loss'].shape == () and got['loss'] == 0.5
+    assert got['ints'].dtype == np.float32 and got['ints'].tolist() == [0, 1, 2, 3, 4, 5]
+    assert got['wide'].dtype == np.float64 and got['wide'].tolist() == [0, 1, 2, 3]
+    big = got['big']
+    assert big.dtype == np.float32 and big.shape == (100,)
+    assert np.all(np.diff(big) > 0) and set(big.tolist()) <= set(range(1000))    # a sample of the elements, in order
+    assert np.array_equal(big, np.load(tmp_path / 'b' / 'big.npy'))              # the same sample every time
+    assert sum(a.nbytes for a in got.values()) <= 4 * 400
+
+
 def test_line_trims_when_strings_grow():
     full = _canned()
     full['cpu_baseline']['sample'] = 'x' * 5000
