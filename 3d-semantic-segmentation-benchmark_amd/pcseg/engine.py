@@ -637,9 +637,59 @@ class EdgeConvFn(torch.autograd.Function):
 
 
 def edgeconv_fused_ok(conv, bn, cin: int) -> bool:
-    """The fused EdgeConv covers training-mode BN (eval-mode BN uses the materialised-edge path)."""
+    """The fused training EdgeConv covers training-mode BN.  Eval-mode BN takes edgeconv_infer
+    under no_grad (edgeconv_infer_ok) and the materialised-edge path when a backward is needed."""
     return (bn.training and conv.weight.shape[0] % 4 == 0 and conv.bias is None
             and (cin % 4 == 0 or cin < 4))
+
+
+def edgeconv_infer_ok(conv, bn, cin: int) -> bool:
+    """The eval-mode EdgeConv kernels (csrc/edgeconv_infer.hip) cover BN on its running statistics,
+    no conv bias, Cout % 4 == 0 up to 128 and cin < 4 or cin % 4 == 0 up to 128."""
+    cout = conv.weight.shape[0]
+    return (not bn.training and bn.running_mean is not None and bn.running_var is not None
+            and bn.weight is not None and bn.bias is not None and conv.bias is None
+            and cout % 4 == 0 and cout <= 128 and (cin < 4 or (cin % 4 == 0 and cin <= 128)))
+
+
+def _check_also(name, also, x_rows, Cout):
+    if (also.dim() != 2 or tuple(also.shape) != (x_rows.shape[0], Cout) or also.stride(1) != 1
+            or also.stride(0) % 4 or also.data_ptr() % 16 or also.device != x_rows.device):
+        raise ValueError(f'{name}: `also` must be a 16-B aligned ({x_rows.shape[0]}, {Cout}) row block '
+                         f'with unit column stride, got {tuple(also.shape)} strides {also.stride()}')
+
+
+def edgeconv_infer(x_rows: torch.Tensor, cin: int, idx: torch.Tensor, conv, bn, slope: float,
+                   also: torch.Tensor | None = None) -> torch.Tensor:
+    """Eval-mode EdgeConv (dgcnn.py:24-77 under model.eval()) outside autograd: x_rows (B*N, ld)
+    point rows (dense, or a column block of a wider buffer), idx (B, N, k) int32 -> pooled
+    (B*N, Cout) = act(max_j U_j + V_i) with BN's running statistics folded into U and V
+    (pcs_edgeconv_infer); nothing is saved and the statistics are only read.  also: as edgeconv's."""
+    if not x_rows.is_cuda:
+        raise RuntimeError('pcseg ops run only on the GPU (no CPU fallback); got a CPU tensor')
+    if not edgeconv_infer_ok(conv, bn, cin):
+        raise ValueError('edgeconv_infer: needs eval-mode BatchNorm with running statistics, no conv bias, '
+                         'Cout % 4 == 0 <= 128 and cin < 4 or cin % 4 == 0 <= 128')
+    x_rows = x_rows.detach()
+    if not (x_rows.dim() == 2 and x_rows.stride(1) == 1 and x_rows.stride(0) % 4 == 0
+            and x_rows.stride(0) >= max(cin, 4) and x_rows.data_ptr() % 16 == 0):
+        x_rows = pad_rows(x_rows[:, :cin])
+    Cout = conv.weight.shape[0]
+    if also is not None:
+        _check_also('edgeconv_infer', also, x_rows, Cout)
+    dev = x_rows.device
+    idx = idx.contiguous()
+    B, N, k = idx.shape
+    M = x_rows.shape[0]
+    Wm = conv.weight.detach().reshape(Cout, 2 * cin)
+    if not Wm.is_contiguous() or (cin >= 4 and Wm.data_ptr() % 16):
+        Wm = Wm.clone(memory_format=torch.contiguous_format)
+    U, V, out = (_f32((M, Cout), dev) for _ in range(3))
+    call('pcs_edgeconv_infer', ptr(x_rows), x_rows.stride(0), cin, ptr(idx), B, N, k, ptr(Wm), Cout,
+         ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps), float(slope),
+         ptr(U), ptr(V), ptr(out), ptr(also) if also is not None else None,
+         also.stride(0) if also is not None else 0, stream_ptr(dev))
+    return out
 
 
 def edgeconv(x_rows: torch.Tensor, cin: int, idx: torch.Tensor, conv, bn, slope: float,
@@ -654,11 +704,7 @@ def edgeconv(x_rows: torch.Tensor, cin: int, idx: torch.Tensor, conv, bn, slope:
     if x_rows.shape[1] % 4 or not x_rows.is_contiguous():
         x_rows = pad_rows(x_rows[:, :cin])
     if also is not None:
-        Cout = conv.weight.shape[0]
-        if (also.dim() != 2 or tuple(also.shape) != (x_rows.shape[0], Cout) or also.stride(1) != 1
-                or also.stride(0) % 4 or also.data_ptr() % 16 or also.device != x_rows.device):
-            raise ValueError(f'edgeconv: `also` must be a 16-B aligned ({x_rows.shape[0]}, {Cout}) row block '
-                             f'with unit column stride, got {tuple(also.shape)} strides {also.stride()}')
+        _check_also('edgeconv', also, x_rows, conv.weight.shape[0])
     return EdgeConvFn.apply(x_rows, idx.contiguous(), cin, slope, bn, conv.weight, bn.weight, bn.bias, inverse_side,
                             holder, (also,) if also is not None else None)
 

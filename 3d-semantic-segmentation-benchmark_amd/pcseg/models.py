@@ -17,8 +17,8 @@ import torch.nn.functional as F
 
 from . import ops
 from .common import SetAbstraction, FeaturePropagation, InvResMLP, UnitPointNet, GeometryPlan, GeometryPrefetch
-from .engine import (shared_mlp, pad_rows, linear_rows, edgeconv, edgeconv_fused_ok, storage_alias, module_cache,
-                     EdgeInverseBatch)
+from .engine import (shared_mlp, pad_rows, linear_rows, edgeconv, edgeconv_fused_ok, edgeconv_infer, edgeconv_infer_ok,
+                     storage_alias, module_cache, EdgeInverseBatch)
 from .replay import active as _replay
 from ._lib import call, ptr, stream_ptr
 
@@ -281,6 +281,12 @@ class EdgeConv(nn.Module):
             pooled = edgeconv(xp.reshape(B * N, C), C, idx, self.conv[0], self.conv[1], self.conv[2].negative_slope,
                               inverse_side=self.edge_inverse == 'side', holder=holder, also=also)
             return pooled.view(B, N, -1), idx
+        if not torch.is_grad_enabled() and edgeconv_infer_ok(self.conv[0], self.conv[1], C):
+            # inference / evaluation: eval-mode BN folded into one point GEMM and one gather-max
+            pooled = edgeconv_infer(xp.reshape(B * N, C), C, idx, self.conv[0], self.conv[1],
+                                    self.conv[2].negative_slope, also=also)
+            return pooled.view(B, N, -1), idx
+        # eval-mode BN with a backward (or a shape the kernels above do not cover): materialised edges
         rows = ops.edge_rows(xp, idx)
         pooled = shared_mlp(rows, 2 * C, [self.conv[0]], [self.conv[1]], 'lrelu',
                             self.conv[2].negative_slope, pool_k=self.k)

@@ -424,6 +424,21 @@ int pcs_edgeconv_bwd(const float* X, int ldx, int C, const int32_t* csr_off,
                      float slope, const float* dout, int ldo, float* dX, int lddx,
                      float* dW, float* dgamma, float* dbeta, void* workspace,
                      size_t ws_bytes, void* stream);
+/* eval-mode forward (BatchNorm2d on its running statistics, no autograd state;
+ * models/dgcnn/dgcnn.py:24-77 under model.eval()): with s = gamma / sqrt(run_var +
+ * eps), t = beta - run_mean s, out_i = act(max_j U_j + V_i), U = s o (X W1^T),
+ * V = s o (X (W2 - W1)^T) + t -- one point-transform GEMM and one gather-max, no
+ * edge tensor.  U, V: caller-owned (B*N, Cout) scratch; out (B*N, Cout); out2
+ * (nullable, row stride ld2 >= Cout, ld2 % 4 == 0) a second copy as in
+ * pcs_edgeconv_fwd.  1 <= k <= N; C < 4 or C % 4 == 0, C <= 128; Cout % 4 == 0,
+ * Cout <= 128 (the folded 2 Cout x C weight lives in one block's LDS); ldx % 4 == 0,
+ * ldx >= C; slope >= 0; X, W (C >= 4), U, V, out, out2 16-B aligned.  Nothing is
+ * allocated and the running statistics are only read. */
+int pcs_edgeconv_infer(const float* X, int ldx, int C, const int32_t* idx, int B, int N,
+                       int k, const float* W, int Cout, const float* gamma,
+                       const float* beta, const float* run_mean, const float* run_var,
+                       float eps, float slope, float* U, float* V, float* out,
+                       float* out2, int ld2, void* stream);
 
 /* ---- launch probe (measurement) -----------------------------------------------
  * While enabled, every engine GEMM launch (pcs_gemm_rows / pcs_wgrad, also those
