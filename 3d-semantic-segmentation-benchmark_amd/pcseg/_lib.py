@@ -93,6 +93,8 @@ SIGNATURES = {
     'pcs_mlp_backward': [P, I32, I32, I32, ctypes.c_char_p, I32, I32, P, P, I32, P, I32, P, ctypes.c_size_t, P],
     'pcs_mlp_backward_deferred': [P, I32, I32, I32, ctypes.c_char_p, I32, I32, P, P, I32, P, I32, P,
                                   ctypes.c_size_t, P],
+    'pcs_group_mlp_infer_lds': [I32, P, I32, I32, P],
+    'pcs_group_mlp_infer': [P, P, P, P, I32, I32, I32, I32, I32, F32, I32, ctypes.c_char_p, I32, P, P],
     'pcs_wgrad_lane': [P],
     'pcs_wgrad_lane_join': [P],
     'pcs_geometry_stream': [P],

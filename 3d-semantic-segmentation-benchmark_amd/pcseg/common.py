@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .engine import shared_mlp, pad_rows, module_cache
+from .engine import shared_mlp, pad_rows, module_cache, group_mlp_infer, group_mlp_infer_ok
 from ._lib import call, stream_ptr
 from .replay import active as _replay
 
@@ -430,6 +430,12 @@ class MiniPointNet(nn.Module):
             self.batch.append(nn.BatchNorm2d(m))
             prev = m
         self.bwd_fuse = 0           # backward kernel choice (pcseg.engine.set_bwd_fuse)
+        self.eval_fuse = False      # fused eval-mode group + stack + max kernel (pcseg.engine.set_eval_fuse)
+
+    def fused_eval(self, kin: int, K: int) -> bool:
+        """Whether a grouped, max-pooled call on kin channels takes group_mlp_infer: opted in, no
+        autograd, eval-mode BN and a covered shape."""
+        return self.eval_fuse and not torch.is_grad_enabled() and group_mlp_infer_ok(self.conv, self.batch, kin, K)
 
     def forward_rows(self, x: torch.Tensor, kin: int | None = None, pool_k: int = 0, dx_from: int = 0) -> torch.Tensor:
         """rows (M, ld) -> (M, C_L), or (M/pool_k, C_L) max-pooled over consecutive groups of pool_k rows.
@@ -495,8 +501,11 @@ class SetAbstraction(nn.Module):
         else:
             cent, idx = geo[0], geo[1]
             inv = geo[2] if len(geo) > 2 else None
-        rows = ops.group_rows(coords, features, cent, idx, self.radius, self.grouping_norm, inv)
         kin = 3 + features.shape[2]
+        if self.pooling_type == 'max' and self.point_net.fused_eval(kin, self.K):
+            return cent, group_mlp_infer(coords, features, cent, idx, self.radius, self.grouping_norm,
+                                         self.point_net.conv, self.point_net.batch).view(B, self.C, -1)
+        rows = ops.group_rows(coords, features, cent, idx, self.radius, self.grouping_norm, inv)
         if self.pooling_type == 'max':
             out = self.point_net.forward_rows(rows, kin, pool_k=self.K, dx_from=3).view(B, self.C, -1)
         else:
@@ -552,8 +561,12 @@ class InvResMLP(nn.Module):
             idx = geo
         else:
             idx, inv = geo
-        rows = ops.group_rows(coords, features, centroid_coords, idx, self.radius, True, inv)
         kin = 3 + features.shape[2]
+        mlp = self.neighbour_features_mlp
+        if self.pooling_type == 'max' and mlp.fused_eval(kin, self.K):
+            pooled = group_mlp_infer(coords, features, centroid_coords, idx, self.radius, True, mlp.conv, mlp.batch)
+            return centroid_coords, self.point_features_mlp.forward_rows(pooled).view(B, C, -1) + features
+        rows = ops.group_rows(coords, features, centroid_coords, idx, self.radius, True, inv)
         if self.pooling_type == 'max':
             pooled = self.neighbour_features_mlp.forward_rows(rows, kin, pool_k=self.K, dx_from=3)
         else:

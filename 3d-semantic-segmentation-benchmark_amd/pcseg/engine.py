@@ -692,6 +692,68 @@ def edgeconv_infer(x_rows: torch.Tensor, cin: int, idx: torch.Tensor, conv, bn, 
     return out
 
 
+def set_eval_fuse(module: torch.nn.Module, on: bool = True) -> None:
+    """Let every MiniPointNet under `module` run its grouped, max-pooled stack through the fused
+    eval-mode kernel (group_mlp_infer) whenever BatchNorm is in eval mode, grad is disabled and the
+    shape is covered (group_mlp_infer_ok).  Off by default: the folded-weight kernel agrees with the
+    layered path to fp32 rounding, not bitwise."""
+    for m in module.modules():
+        if hasattr(m, 'eval_fuse'):
+            m.eval_fuse = bool(on)
+
+
+def group_mlp_infer_ok(convs, bns, kin: int, K: int) -> bool:
+    """The fused eval-mode grouped MLP + max-pool (csrc/group_mlp_infer.hip) covers 1..3 ReLU layers
+    of width % 4 == 0 up to 128 on 4 <= kin = 3 + D <= 132 channels, K 16 or 32, BatchNorm on its
+    running statistics, and stacks whose folded weights and activation tiles fit one CU's LDS
+    (pcs_group_mlp_infer_lds, the only holder of that limit)."""
+    if not 1 <= len(convs) == len(bns) <= 3:
+        return False
+    for bn in bns:
+        if (bn.training or bn.running_mean is None or bn.running_var is None or bn.weight is None
+                or bn.bias is None):
+            return False
+    widths = tuple(int(c.weight.shape[0]) for c in convs)
+    key = ('gmi', int(kin), widths, int(K))
+    ok = _ws_cache.get(key)
+    if ok is None:
+        out = ctypes.c_size_t(0)
+        ok = _ws_cache[key] = load().pcs_group_mlp_infer_lds(int(kin), (ctypes.c_int * len(widths))(*widths),
+                                                             len(widths), int(K), ctypes.byref(out)) == 0
+    return ok
+
+
+def group_mlp_infer(xyz: torch.Tensor, feats: torch.Tensor, cent: torch.Tensor, idx: torch.Tensor, r: float,
+                    normalize: bool, convs, bns) -> torch.Tensor:
+    """Eval-mode SetAbstraction stack outside autograd (common.py:180-214 under model.eval()): xyz
+    (B, N, 3), feats (B, N, D), cent (B, C, 3), idx (B, C, K) int32 -> (B*C, cout_L) =
+    max_j relu(BN(conv(..[(xyz[idx] - cent) (/ r), feats[idx]]..))) in one kernel, BatchNorm's running
+    statistics folded into the weights; nothing else is written and the statistics are only read."""
+    if not (xyz.is_cuda and feats.is_cuda and cent.is_cuda and idx.is_cuda):
+        raise RuntimeError('pcseg ops run only on the GPU (no CPU fallback); got a CPU tensor')
+    B, N, _ = xyz.shape
+    C, K = idx.shape[1], idx.shape[2]
+    D = feats.shape[2]
+    if not group_mlp_infer_ok(convs, bns, 3 + D, K):
+        raise ValueError('group_mlp_infer: needs eval-mode BatchNorm with running statistics, 1..3 layers of '
+                         'width % 4 == 0 <= 128, 3 + D <= 132, K 16 or 32 and a stack that fits the LDS')
+    dev = xyz.device
+    xyz, feats, cent = (t.detach().float().contiguous() for t in (xyz, feats, cent))
+    idx = idx.contiguous()
+    if idx.dtype != torch.int32:
+        idx = idx.int()
+    params = []
+    for conv, bn in zip(convs, bns):
+        params += [conv.weight, conv.bias, bn.weight, bn.bias]
+    couts = [c.weight.shape[0] for c in convs]
+    statics, Wms, _ = _layer_statics(3 + D, bns, ((ACT['relu'], 0.0),) * len(convs), params, couts, dev)
+    recs = b''.join(s + _DYN.pack(0, 0, 0, 0, 0, 0, 0.0, 0, 0, 0) for s in statics)
+    out = _f32((B * C, couts[-1]), dev)
+    call('pcs_group_mlp_infer', ptr(xyz), ptr(feats), ptr(cent), ptr(idx), B, N, C, K, D, float(r),
+         int(bool(normalize)), recs, len(convs), ptr(out), stream_ptr(dev))
+    return out
+
+
 def edgeconv(x_rows: torch.Tensor, cin: int, idx: torch.Tensor, conv, bn, slope: float,
              inverse_side: bool = True, holder: list | None = None, also: torch.Tensor | None = None) -> torch.Tensor:
     """x_rows (B*N, ld) point rows, idx (B, N, k) int32 -> pooled (B*N, Cout).  inverse_side: build

@@ -18,7 +18,7 @@ import torch.nn.functional as F
 from . import ops
 from .common import SetAbstraction, FeaturePropagation, InvResMLP, UnitPointNet, GeometryPlan, GeometryPrefetch
 from .engine import (shared_mlp, pad_rows, linear_rows, edgeconv, edgeconv_fused_ok, edgeconv_infer, edgeconv_infer_ok,
-                     storage_alias, module_cache, EdgeInverseBatch)
+                     group_mlp_infer, storage_alias, module_cache, EdgeInverseBatch)
 from .replay import active as _replay
 from ._lib import call, ptr, stream_ptr
 
@@ -119,6 +119,10 @@ class PointNetppMSG(GeometryPrefetch, nn.Module):
         outs = []
         for q, sa in enumerate(branches):
             cent, idx, inv = geo.sa(level, q)
+            if sa.pooling_type == 'max' and sa.point_net.fused_eval(3 + feats.shape[2], sa.K):
+                outs.append(group_mlp_infer(coords, feats, cent, idx, sa.radius, sa.grouping_norm, sa.point_net.conv,
+                                            sa.point_net.batch).view(B, C, -1))
+                continue
             rows = ops.group_rows(coords, feats, cent, idx, sa.radius, sa.grouping_norm, inv)
             outs.append(sa.point_net.forward_rows(rows, 3 + feats.shape[2], pool_k=sa.K, dx_from=3).view(B, C, -1))
         return cent, torch.cat(outs, dim=-1)

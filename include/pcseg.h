@@ -355,6 +355,21 @@ int pcs_mlp_backward_deferred(const float* X, int ldx, int kin, int M,
                               const pcs_mlp_layer* layers, int nl, int pool_k,
                               const uint8_t* arg, const float* gout, int ldg, float* dX, int lddx,
                               void* workspace, size_t ws_bytes, void* stream);
+/* Eval-mode SetAbstraction stack in ONE kernel (common.py:37-71, 125-150, 180-214 under
+ * model.eval()): gather [ (xyz[idx] - cent) (/ r if normalize), feats[idx] ] (3 + D channels,
+ * the arithmetic of pcs_group_fwd), nl <= 3 layers relu(BN(conv)) with BatchNorm on its running
+ * statistics folded into the conv, max over the K neighbours; only out (B*C x cout_nl) is
+ * written.  xyz (B, N, 3), feats (B, N, D), cent (B, C, 3), idx (B, C, K) int32 (clamped to the
+ * cloud).  layers: fields W .. slope of each record (bias nullable; use_batch must be 0, act
+ * ReLU; Z, coef and the gradients are not read; the running statistics are only read).
+ * K 16 or 32; D >= 1, 3 + D <= 132; every width % 4 == 0 and <= 128; the folded weights and
+ * two activation tiles must fit one CU's LDS: pcs_group_mlp_infer_lds returns the bytes for a
+ * stack on kin = 3 + D channels, or non-zero (with a message) when the shape is not covered. */
+int pcs_group_mlp_infer_lds(int kin, const int* widths, int nl, int K, size_t* bytes);
+int pcs_group_mlp_infer(const float* xyz, const float* feats, const float* cent,
+                        const int32_t* idx, int B, int N, int C, int K, int D, float r,
+                        int normalize, const pcs_mlp_layer* layers, int nl, float* out,
+                        void* stream);
 /* the current device's wgrad lane stream (null if none could be created) */
 int pcs_wgrad_lane(void** side_stream);
 /* `stream` waits for every weight gradient enqueued on the current device's lane so far */
