@@ -11,7 +11,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .engine import shared_mlp, pad_rows, module_cache, group_mlp_infer, group_mlp_infer_ok
+from .engine import (shared_mlp, pad_rows, module_cache, group_mlp_infer, group_mlp_infer_ok, rows_infer_ok,
+                     rows_infer_stack)
 from ._lib import call, stream_ptr
 from .replay import active as _replay
 
@@ -463,11 +464,18 @@ class UnitPointNet(nn.Module):
             self.batch.append(nn.BatchNorm1d(m))
             prev = m
         self.bwd_fuse = 0           # backward kernel choice (pcseg.engine.set_bwd_fuse)
+        self.eval_gemm = 'fp32'     # 'bf16x3': the split-bf16 eval-mode kernel (pcseg.engine.set_eval_gemm)
+        self.eval_gemm_rows = 0     # ... for calls on at least this many rows
 
     def forward_rows(self, x: torch.Tensor, kin: int | None = None, dropout: tuple | None = None,
                      dx_from: int = 0) -> torch.Tensor:
         """dropout = (p, seed): a training-mode Dropout after the stack, fused into its output.
         dx_from: the first input column whose gradient is wanted (pcs_mlp_layer.dx_col0)."""
+        if self.eval_gemm == 'bf16x3' and dropout is None and not torch.is_grad_enabled():
+            cins = [kin or x.shape[1]] + [c.weight.shape[0] for c in self.conv[:-1]]
+            if all(rows_infer_ok(c, b, k, x.shape[0], self.eval_gemm_rows)
+                   for c, b, k in zip(self.conv, self.batch, cins)):
+                return rows_infer_stack(x, cins[0], self.conv, self.batch, 'relu', 0.0)
         return shared_mlp(x, kin or x.shape[1], self.conv, self.batch, 'relu', 0.0, 0, dropout=dropout,
                           bwd_fuse=self.bwd_fuse, cache=module_cache(self), dx_from=dx_from)
 

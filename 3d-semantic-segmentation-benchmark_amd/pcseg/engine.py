@@ -754,6 +754,86 @@ def group_mlp_infer(xyz: torch.Tensor, feats: torch.Tensor, cent: torch.Tensor, 
     return out
 
 
+EVAL_GEMM = ('fp32', 'bf16x3')
+# rows from which a rows_infer launch beat the engine launches it replaces (every covered
+# layer at >= 16384 rows won, every one at <= 4096 rows -- at most 64 of the kernel's 128 x 128 tiles on 256
+# CUs -- lost or tied)
+ROWS_INFER_MIN_ROWS = 16384
+
+
+def set_eval_gemm(module: torch.nn.Module, mode: str = 'bf16x3', min_rows: int = ROWS_INFER_MIN_ROWS) -> None:
+    """Which GEMM the un-pooled eval-mode layers under `module` run on (`eval_gemm` of every UnitPointNet,
+    DGCNN / DGCNNWithColor head and PointNet++-family classifier): 'fp32', the engine's fp32 MFMA GEMMs
+    (the default), or 'bf16x3', the split-bf16 kernel (rows_infer) whenever BatchNorm is in eval mode,
+    grad is disabled and rows_infer_ok holds for the call's row count.  min_rows (`eval_gemm_rows`): calls
+    on fewer rows keep the engine.  'bf16x3' agrees with 'fp32' to ~5e-6 norm-relative per layer, not
+    bitwise."""
+    if mode not in EVAL_GEMM:
+        raise ValueError(f'eval gemm must be one of {EVAL_GEMM}, got {mode!r}')
+    for m in module.modules():
+        if hasattr(m, 'eval_gemm'):
+            m.eval_gemm = mode
+            m.eval_gemm_rows = int(min_rows)
+
+
+def rows_infer_ok(conv, bn, cin: int, rows: int | None = None, min_rows: int = ROWS_INFER_MIN_ROWS) -> bool:
+    """The split-bf16 eval-mode layer (csrc/rows_infer.hip) covers a 1x1 conv on cin % 4 == 0 channels
+    with cout % 4 == 0, followed by a BatchNorm on its running statistics, or by none (bn None).  With
+    `rows` (a dispatcher's row count) also: at least min_rows rows, below which the engine is faster."""
+    W = conv.weight
+    cout = W.shape[0]
+    if rows is not None and rows < min_rows:
+        return False
+    if cin < 4 or cin % 4 or cout < 4 or cout % 4 or W.numel() != cout * cin:
+        return False
+    return bn is None or (not bn.training and bn.running_mean is not None and bn.running_var is not None
+                          and bn.weight is not None and bn.bias is not None)
+
+
+def rows_infer(x_rows: torch.Tensor, kin: int, conv, bn, act: str = 'relu', slope: float = 0.0,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """One eval-mode layer outside autograd: x_rows (M, ld) with kin channels, dense or a column block
+    of a wider buffer -> act(BN(conv(x))) (M, cout) on the bf16 matrix pipe with split operands
+    (pcs_rows_infer); bn None: conv with its bias only.  `out`: an (M, cout) row block (storage_alias)
+    the result is written into.  Nothing is saved, recorded or updated."""
+    if not x_rows.is_cuda:
+        raise RuntimeError('pcseg ops run only on the GPU (no CPU fallback); got a CPU tensor')
+    if not rows_infer_ok(conv, bn, kin):
+        raise ValueError('rows_infer: needs cin % 4 == 0, cout % 4 == 0 and an eval-mode BatchNorm with running '
+                         'statistics (or none)')
+    x_rows = x_rows.detach()
+    if not (x_rows.dim() == 2 and x_rows.stride(1) == 1 and x_rows.stride(0) % 4 == 0 and x_rows.stride(0) >= kin
+            and x_rows.shape[1] >= kin and x_rows.data_ptr() % 16 == 0):
+        x_rows = x_rows[:, :kin].contiguous()
+    M = x_rows.shape[0]
+    cout = conv.weight.shape[0]
+    dev = x_rows.device
+    if out is None:
+        out = _f32((M, cout), dev)
+    elif not _rows_ok(out) or out.shape != (M, cout):
+        raise ValueError('rows_infer: out must be an (M, cout) row block')
+    if M == 0:
+        return out
+    Wm = conv.weight.detach().reshape(cout, kin)
+    if not Wm.is_contiguous() or Wm.data_ptr() % 16:
+        Wm = Wm.clone(memory_format=torch.contiguous_format)
+    bnp = (bn.weight, bn.bias, bn.running_mean, bn.running_var) if bn is not None else (None,) * 4
+    rec = _REC.pack(Wm.data_ptr(), kin, kin, cout, _nz(conv.bias), *(_nz(p) for p in bnp), 0, 0.0,
+                    float(bn.eps) if bn is not None else 0.0, 0, ACT[act], float(slope), 0, 0, 0, 0, 0, 0, 0.0, 0, 0, 0)
+    call('pcs_rows_infer', ptr(x_rows), x_rows.stride(0), M, rec, ptr(out), out.stride(0), stream_ptr(dev))
+    return out
+
+
+def rows_infer_stack(x_rows: torch.Tensor, kin: int, convs, bns, act: str = 'relu', slope: float = 0.0,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+    """A stack of eval-mode layers, one rows_infer launch each; the intermediate activations are
+    ordinary temporaries and `out` receives the last layer's."""
+    for li, (conv, bn) in enumerate(zip(convs, bns)):
+        x_rows = rows_infer(x_rows, kin, conv, bn, act, slope, out if li == len(convs) - 1 else None)
+        kin = conv.weight.shape[0]
+    return x_rows
+
+
 def edgeconv(x_rows: torch.Tensor, cin: int, idx: torch.Tensor, conv, bn, slope: float,
              inverse_side: bool = True, holder: list | None = None, also: torch.Tensor | None = None) -> torch.Tensor:
     """x_rows (B*N, ld) point rows, idx (B, N, k) int32 -> pooled (B*N, Cout).  inverse_side: build

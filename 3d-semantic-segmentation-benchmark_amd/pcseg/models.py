@@ -18,13 +18,22 @@ import torch.nn.functional as F
 from . import ops
 from .common import SetAbstraction, FeaturePropagation, InvResMLP, UnitPointNet, GeometryPlan, GeometryPrefetch
 from .engine import (shared_mlp, pad_rows, linear_rows, edgeconv, edgeconv_fused_ok, edgeconv_infer, edgeconv_infer_ok,
-                     group_mlp_infer, storage_alias, module_cache, EdgeInverseBatch)
+                     group_mlp_infer, storage_alias, module_cache, EdgeInverseBatch, rows_infer, rows_infer_ok)
 from .replay import active as _replay
 from ._lib import call, ptr, stream_ptr
 
 
-def _head_rows(x_rows: torch.Tensor, drop: nn.Module | None, conv: nn.Module) -> torch.Tensor:
-    return linear_rows(drop(x_rows) if drop is not None else x_rows, conv)
+def _bf16x3(gemm: tuple, conv: nn.Module, bn: nn.Module | None, cin: int, rows: int) -> bool:
+    """Whether an un-pooled layer takes the split-bf16 eval-mode kernel: opted in (gemm = the model's
+    (eval_gemm, eval_gemm_rows)), no autograd, eval-mode BN (or none) and a covered shape."""
+    return gemm[0] == 'bf16x3' and not torch.is_grad_enabled() and rows_infer_ok(conv, bn, cin, rows, gemm[1])
+
+
+def _head_rows(x_rows: torch.Tensor, drop: nn.Module | None, conv: nn.Module, gemm: tuple = ('fp32', 0)) -> torch.Tensor:
+    x_rows = drop(x_rows) if drop is not None else x_rows
+    if _bf16x3(gemm, conv, None, x_rows.shape[1], x_rows.shape[0]):
+        return rows_infer(x_rows, x_rows.shape[1], conv, None, 'none')
+    return linear_rows(x_rows, conv)
 
 
 def _fused_dropout(drop: nn.Module):
@@ -52,6 +61,7 @@ class PointNetpp(GeometryPrefetch, nn.Module):
         self.fp1 = FeaturePropagation(128, [128, 128, 128, 128])
         self.drop = nn.Dropout(0.5)
         self.conv = nn.Conv1d(128, part_classes, 1)
+        self.eval_gemm, self.eval_gemm_rows = 'fp32', 0     # pcseg.engine.set_eval_gemm: the classifier's GEMM
 
     def _plan_for(self, c0, inverse=True, into=None):
         return GeometryPlan(c0, [(sa.C, [(sa.radius, sa.K, False)]) for sa in (self.sa1, self.sa2, self.sa3, self.sa4)],
@@ -72,7 +82,8 @@ class PointNetpp(GeometryPrefetch, nn.Module):
         f1 = self._prefetch_point(self.fp2(c1, c2, f1, f2, geo=geo.fp(1)))
         dz = _fused_dropout(self.drop)       # the head's Dropout, fused into FP1's output
         f0 = self.fp1(c0, c1, None, f1, geo=geo.fp(0), dropout=dz)
-        return _head_rows(f0.reshape(B * N, -1), None if dz else self.drop, self.conv).view(B, N, -1)
+        gemm = (self.eval_gemm, self.eval_gemm_rows)
+        return _head_rows(f0.reshape(B * N, -1), None if dz else self.drop, self.conv, gemm).view(B, N, -1)
 
 
 class PointNetppMSG(GeometryPrefetch, nn.Module):
@@ -108,6 +119,7 @@ class PointNetppMSG(GeometryPrefetch, nn.Module):
         self.fp1 = FeaturePropagation(128, [128, 128, 128])
         self.drop = nn.Dropout(0.5)
         self.conv = nn.Conv1d(128, part_classes, 1)
+        self.eval_gemm, self.eval_gemm_rows = 'fp32', 0     # pcseg.engine.set_eval_gemm: the classifier's GEMM
 
     def _plan_for(self, c0, inverse=True, into=None):
         return GeometryPlan(c0, [(br[0].C, [(sa.radius, sa.K, False) for sa in br]) for br in self.levels],
@@ -141,7 +153,8 @@ class PointNetppMSG(GeometryPrefetch, nn.Module):
         f1 = self._prefetch_point(self.fp2(cs[1], cs[2], fs[1], f2, geo=geo.fp(1)))
         dz = _fused_dropout(self.drop)       # the head's Dropout, fused into FP1's output
         f0 = self.fp1(cs[0], cs[1], None, f1, geo=geo.fp(0), dropout=dz)
-        return _head_rows(f0.reshape(B * N, -1), None if dz else self.drop, self.conv).view(B, N, -1)
+        gemm = (self.eval_gemm, self.eval_gemm_rows)
+        return _head_rows(f0.reshape(B * N, -1), None if dz else self.drop, self.conv, gemm).view(B, N, -1)
 
 
 class PointNeXt(GeometryPrefetch, nn.Module):
@@ -175,6 +188,7 @@ class PointNeXt(GeometryPrefetch, nn.Module):
         fp1 = self.fp1.point_net.conv[-1].out_channels
         self.drop = nn.Dropout(0.5)
         self.conv = nn.Conv1d(fp1, part_classes, 1)
+        self.eval_gemm, self.eval_gemm_rows = 'fp32', 0     # pcseg.engine.set_eval_gemm: the classifier's GEMM
 
     def _plan_for(self, c0, inverse=True, into=None):
         def q(m, on_self):
@@ -206,14 +220,19 @@ class PointNeXt(GeometryPrefetch, nn.Module):
         f1 = self._prefetch_point(self.fp2(c1, c2, f1, f2, geo=geo.fp(1)))
         dz = _fused_dropout(self.drop)       # the head's Dropout, fused into FP1's output
         f0 = self.fp1(c0, c1, f0, f1, geo=geo.fp(0), dropout=dz)
-        return _head_rows(f0.reshape(B * N, -1), None if dz else self.drop, self.conv).view(B, N, -1)
+        gemm = (self.eval_gemm, self.eval_gemm_rows)
+        return _head_rows(f0.reshape(B * N, -1), None if dz else self.drop, self.conv, gemm).view(B, N, -1)
 
 
 # ------------------------------------------------------------------------- DGCNN
 def _seq_rows(x_rows: torch.Tensor, seq: nn.Sequential, kin: int | None = None,
-              out: torch.Tensor | None = None) -> torch.Tensor:
+              out: torch.Tensor | None = None, gemm: tuple = ('fp32', 0)) -> torch.Tensor:
     """Conv1d(bias=False) -> BN1d -> LeakyReLU [-> Dropout] on rows (HIP shared-MLP engine);
-    `out`: a row block the activation is written into (no Dropout after it)."""
+    `out`: a row block the activation is written into (no Dropout after it).  gemm: the model's
+    (eval_gemm, eval_gemm_rows) ('bf16x3': the split-bf16 kernel under eval() + no_grad)."""
+    if _bf16x3(gemm, seq[0], seq[1], kin or x_rows.shape[1], x_rows.shape[0]):
+        y = rows_infer(x_rows, kin or x_rows.shape[1], seq[0], seq[1], 'lrelu', seq[2].negative_slope, out=out)
+        return seq[3](y) if len(seq) > 3 else y
     # training-mode Dropout fused into the stack's output
     drop = _fused_dropout(seq[3]) if len(seq) > 3 and out is None else None
     y = shared_mlp(x_rows, kin or x_rows.shape[1], [seq[0]], [seq[1]], 'lrelu', seq[2].negative_slope, 0, out=out,
@@ -392,10 +411,11 @@ def _dgcnn_head(self, parts: list[torch.Tensor], B: int, N: int, H: torch.Tensor
     if H is None:
         H = torch.empty((M, cxr + emb), dtype=torch.float32, device=parts[0].device)
     xr = _CopyColumns.apply((storage_alias(H, 0, cxr), (written,) * len(parts)), *parts)  # (B*N, 320|384), stride 1344|1408
-    x5 = _seq_rows(xr, self.conv5, out=storage_alias(H, cxr, emb))        # (B*N, emb)
-    x6 = _seq_rows(_ColumnConcat.apply(xr, x5), self.conv6)
-    x7 = _seq_rows(x6, self.conv7)
-    logits = linear_rows(x7, self.conv8).view(B, N, -1)
+    gemm = (self.eval_gemm, self.eval_gemm_rows)
+    x5 = _seq_rows(xr, self.conv5, out=storage_alias(H, cxr, emb), gemm=gemm)        # (B*N, emb)
+    x6 = _seq_rows(_ColumnConcat.apply(xr, x5), self.conv6, gemm=gemm)
+    x7 = _seq_rows(x6, self.conv7, gemm=gemm)
+    logits = _head_rows(x7, None, self.conv8, gemm).view(B, N, -1)
     # the reference returns x5 as a contiguous (B, emb, N); a transposed view of
     # the point-major rows has the same shape and values without a 0.5 GB copy
     return logits, x5.view(B, N, -1).transpose(1, 2), None
@@ -429,6 +449,7 @@ class DGCNN(nn.Module):
         self.conv6 = _head_seq(emb_dims + 320, 512, dropout)
         self.conv7 = _head_seq(512, 256, dropout)
         self.conv8 = nn.Conv1d(256, num_classes, kernel_size=1)
+        self.eval_gemm, self.eval_gemm_rows = 'fp32', 0     # pcseg.engine.set_eval_gemm: the head's GEMMs
 
     def forward(self, x):
         B, _, N = x.shape
@@ -464,6 +485,7 @@ class DGCNNWithColor(nn.Module):
         self.conv6 = _head_seq(emb_dims + 384, 512, dropout)
         self.conv7 = _head_seq(512, 256, dropout)
         self.conv8 = nn.Conv1d(256, num_classes, kernel_size=1)
+        self.eval_gemm, self.eval_gemm_rows = 'fp32', 0     # pcseg.engine.set_eval_gemm: the head's GEMMs
 
     def forward(self, x):
         if x.size(1) != 6:
@@ -483,7 +505,8 @@ class DGCNNWithColor(nn.Module):
         x4, _ = self.conv4.forward_graph(x3, g, inv_batch=ib, also=blk[3])       # full scan (note above DGCNN)
         ib.flush()
         # the colour branch's activation lands in its block directly (the head's only reader)
-        color = _seq_rows(pad_rows(rgb.view(B * N, 3)), self.color_conv, 3, out=blk[4])
+        color = _seq_rows(pad_rows(rgb.view(B * N, 3)), self.color_conv, 3, out=blk[4],
+                          gemm=(self.eval_gemm, self.eval_gemm_rows))
         return _dgcnn_head(self, [x1, x2, x3, x4, color], B, N, H)
 
 

@@ -370,6 +370,18 @@ int pcs_group_mlp_infer(const float* xyz, const float* feats, const float* cent,
                         const int32_t* idx, int B, int N, int C, int K, int D, float r,
                         int normalize, const pcs_mlp_layer* layers, int nl, float* out,
                         void* stream);
+/* Eval-mode layer on rows on the bf16 matrix pipe (UnitPointNet, common.py:153-178, and DGCNN's
+ * head, dgcnn.py:188-210, under model.eval()): Y (M x cout, row stride ldy) = act(s o (X W^T) + t),
+ * s = gamma / sqrt(run_var + eps), t = s o (bias - run_mean) + beta, with X (M x cin, row stride
+ * ldx) and the fields W .. slope of ONE record (bias nullable; use_batch must be 0; Z, coef and the
+ * gradients are not read; W and the running statistics are only read).  gamma, beta, run_mean and
+ * run_var all null: a bare linear layer, s = 1, t = bias.  Storage stays fp32: each operand is split
+ * x = hi + lo into two bf16 on its way into LDS and x w ~= hi hi + hi lo + lo hi is accumulated in
+ * fp32 (about 16 significand bits per operand; ~4e-6 norm-relative against fp64 for any cin).
+ * X and Y may be column blocks of wider buffers.  cin, cout >= 4 and % 4 == 0; ldx, ldw, ldy
+ * % 4 == 0; X, W, Y 16-B aligned; act 0 / 1 (slope >= 0) / 2.  Nothing is allocated. */
+int pcs_rows_infer(const float* X, int ldx, long long M, const pcs_mlp_layer* layer, float* Y,
+                   int ldy, void* stream);
 /* the current device's wgrad lane stream (null if none could be created) */
 int pcs_wgrad_lane(void** side_stream);
 /* `stream` waits for every weight gradient enqueued on the current device's lane so far */
