@@ -140,6 +140,10 @@ static bool materialize_dz_of(const pcs_mlp_layer& P, int M, bool dgrad) {
 // measured 4.80 ms with it against 4.55 ms on the default dgrad + lane-wgrad pair
 static bool ring_wanted(int policy) { return policy == PCS_BWD_FUSE_ALL; }
 
+// the two halves of pcs_mlp_layer.bwd_fuse: the fuse policy (low byte) and the wide-GEMM choice
+static int fuse_policy(const pcs_mlp_layer& P) { return (int)(P.bwd_fuse & PCS_BWD_FUSE_MASK); }
+static int wide_bf16x3(const pcs_mlp_layer& P) { return (P.bwd_fuse & PCS_GEMM_BF16X3) ? 1 : 0; }
+
 // Rotation depth of a backward's dA / kB / alpha buffers.  The dgrad of layer l reuses the buffers
 // that layer l + kRot - 1's wgrad reads, so it must wait for that wgrad on the lane; with kRot = 6 no
 // stack of the models (<= 5 layers) ever waits.  (Round 4 rotated over 3: the dgrads of FP1's first two
@@ -305,7 +309,8 @@ static int check_layers(int M, int kin, int ldx, const pcs_mlp_layer* L, int nl,
         PCS_CHECK_ARG(L[l].use_batch || (L[l].run_mean && L[l].run_var),
                       "%s: layer %d: eval-mode BatchNorm needs running statistics", who, l);
         PCS_CHECK_ARG(L[l].act >= 0 && L[l].act <= 2, "%s: layer %d: act=%lld", who, l, (long long)L[l].act);
-        PCS_CHECK_ARG(L[l].bwd_fuse >= PCS_BWD_FUSE_DEFAULT && L[l].bwd_fuse <= PCS_BWD_FUSE_ALL,
+        PCS_CHECK_ARG((L[l].bwd_fuse & ~(int64_t)(PCS_BWD_FUSE_MASK | PCS_GEMM_BF16X3)) == 0 &&
+                          (L[l].bwd_fuse & PCS_BWD_FUSE_MASK) <= PCS_BWD_FUSE_ALL,
                       "%s: layer %d: bwd_fuse=%lld", who, l, (long long)L[l].bwd_fuse);
         cin = (int)L[l].cout;
     }
@@ -360,7 +365,7 @@ PCS_API int pcs_mlp_forward(const float* X, int ldx, int kin, int M, pcs_mlp_lay
         if (P.use_batch) {
             const int nb = pcs_gemm_row_blocks(M, C);
             if (int e = gemm_rows_ex(&a, M, K, P.W, (int)P.ldw, 0, P.bias, P.Z, C, C, part, nullptr, nullptr, stream,
-                                     pz, pa, pk, P.gamma))
+                                     pz, pa, pk, P.gamma, wide_bf16x3(P)))
                 return e;
             const bool track = P.run_mean != nullptr;
             bn_finalize_launch(part, nb, C, M, P.gamma, P.beta, (float)P.eps, track ? (float)P.momentum : 0.f,
@@ -368,7 +373,7 @@ PCS_API int pcs_mlp_forward(const float* X, int ldx, int kin, int M, pcs_mlp_lay
                                reinterpret_cast<long long*>(P.num_batches), st);
         } else {
             if (int e = gemm_rows_ex(&a, M, K, P.W, (int)P.ldw, 0, P.bias, P.Z, C, C, nullptr, nullptr, nullptr, stream,
-                                     pz, pa, pk, P.gamma))
+                                     pz, pa, pk, P.gamma, wide_bf16x3(P)))
                 return e;
             hipLaunchKernelGGL(bn_eval_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, st, P.run_mean, P.run_var,
                                P.gamma, P.beta, (float)P.eps, C, s);
@@ -430,8 +435,8 @@ static int mlp_backward(const float* X, int ldx, int kin, int M, const pcs_mlp_l
                 pcs_operand q = bnbwd_op(nullptr, 0, layers[nl - 2], nullptr, nullptr);
                 q.data = layers[nl - 2].Z;
                 q.ld = (int)T.cin;
-                fused_top = ring_wanted((int)T.bwd_fuse) && bwd_ring_ok(M, CL, (int)T.cin, T.W, (int)T.ldw, &xt, &q);
-                fused_top = fused_top || (fused_bwd_wanted((int)T.bwd_fuse, M) &&
+                fused_top = ring_wanted(fuse_policy(T)) && bwd_ring_ok(M, CL, (int)T.cin, T.W, (int)T.ldw, &xt, &q);
+                fused_top = fused_top || (fused_bwd_wanted(fuse_policy(T), M) &&
                                           fused_bwd_ok(M, CL, (int)T.cin, (int)T.ldw, &xt, &q));
             }
             drop_on_load = !fused_top && materialize_dz_of(T, M, nl > 1 || dX) && S.dz;
@@ -494,9 +499,9 @@ static int mlp_backward(const float* X, int ldx, int kin, int M, const pcs_mlp_l
             qop.ld = Cin;
         }
         // a 128-wide BNBWD inner layer: data + weight gradient on the LDS-DMA ring (bwd_ring.hip)
-        const bool ring = l > 0 && P.dW && ring_wanted((int)P.bwd_fuse) &&
+        const bool ring = l > 0 && P.dW && ring_wanted(fuse_policy(P)) &&
                           bwd_ring_ok(M, C, Cin, P.W, (int)P.ldw, &xop, &qop);
-        const bool fused = ring || (l > 0 && P.dW && fused_bwd_wanted((int)P.bwd_fuse, M) &&
+        const bool fused = ring || (l > 0 && P.dW && fused_bwd_wanted(fuse_policy(P), M) &&
                                     fused_bwd_ok(M, C, Cin, (int)P.ldw, &xop, &qop));
         if (!fused && materialize_dz_of(P, M, l > 0 || dX) && S.dz_ok(l == nl - 1)) {
             // the top layer's into its own buffer (gout is the caller's), inner ones in place
@@ -514,7 +519,7 @@ static int mlp_backward(const float* X, int ldx, int kin, int M, const pcs_mlp_l
         const bool wg_here = l == 0 && !dX && nl > 1;
         if (fused) {
             // its wgrad is part of the fused launch below
-        } else if (P.dW && wg_here && fused_bwd_wanted((int)P.bwd_fuse, M) && fused_wgrad_ok(M, C, Cin, ldx, &xop)) {
+        } else if (P.dW && wg_here && fused_bwd_wanted(fuse_policy(P), M) && fused_wgrad_ok(M, C, Cin, ldx, &xop)) {
             if (int e = fused_wgrad(&xop, C, X, ldx, Cin, M, P.dW, P.db, S.fw, S.fw_bytes, st)) return fail(e);
         } else if (P.dW && wg_here) {
             const pcs_operand y = plain_op(X, ldx);
@@ -600,7 +605,8 @@ static int mlp_backward(const float* X, int ldx, int kin, int M, const pcs_mlp_l
                     hipLaunchKernelGGL(transpose_kernel, g, dim3(256), 0, st, P.W, C, Cin, (int)P.ldw, S.wt);
                 }
                 if (int e = gemm_rows_ex(&xop, M, C, S.wt + (size_t)c0 * C, C, 0, nullptr, dX + c0, lddx, kin - c0,
-                                         nullptr, nullptr, nullptr, stream))
+                                         nullptr, nullptr, nullptr, stream, nullptr, nullptr, 0, nullptr,
+                                         wide_bf16x3(P)))
                     return fail(e);
             } else if (c0 > 0 && (c0 * C) % 4 == 0) {
                 if (bt) {

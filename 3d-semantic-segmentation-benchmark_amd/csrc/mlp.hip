@@ -1278,7 +1278,7 @@ int pcs::materialize_dz(const pcs_operand* x, int M, int C, float* out, int ldo,
 // (B[k][n] = W[k*ldw + n], ldw >= N) -- the data-gradient GEMM on the layer's own weights.
 int pcs::gemm_rows_ex(const pcs_operand* a, int M, int K, const float* W, int ldw, int bt, const float* bias, float* C,
                  int ldc, int N, double* stats, const pcs_operand* epi, double* bstats, void* stream, float* pz,
-                 unsigned char* pa, int pool_k, const float* psign) {
+                 unsigned char* pa, int pool_k, const float* psign, int bf16x3) {
     PCS_CHECK_ARG(pool_k == 0 || ((pool_k == 16 || pool_k == 32) && M % pool_k == 0 && pz && pa && !bt),
                   "pcs_gemm_rows: fused pooling needs pool_k 16|32 dividing M and pz/pa");
     PCS_CHECK_ARG(M >= 0 && K >= 1 && N >= 1, "pcs_gemm_rows: bad sizes M=%d K=%d N=%d", M, K, N);
@@ -1296,6 +1296,8 @@ int pcs::gemm_rows_ex(const pcs_operand* a, int M, int K, const float* W, int ld
     hipStream_t s = as_stream(stream);
     // plain operands of a wide layer, no fused epilogue but BN statistics: the LDS-DMA wide GEMM
     if (!bt && a->mode == PCS_OP_PLAIN && !pool_k && !bstats && gemm_nt_ok(a->data, a->ld, W, ldw, M, N, K)) {
+        // the layer's opt-in (PCS_GEMM_BF16X3): the split-bf16 kernel, same operands and statistics layout
+        if (bf16x3) return gemm_nt_bf16x3(a->data, a->ld, W, ldw, M, N, K, bias, C, ldc, stats, s);
         int probe = -1;
         if (probe_enabled()) {
             char nm[96];

@@ -196,7 +196,8 @@ int materialize_dz(const pcs_operand* x, int M, int C, float* out, int ldo, hipS
 // row GEMM with W row-major N x K (bt = 0, = pcs_gemm_rows) or K x N (bt = 1)
 int gemm_rows_ex(const pcs_operand* a, int M, int K, const float* W, int ldw, int bt, const float* bias, float* C,
                  int ldc, int N, double* stats, const pcs_operand* epi, double* bstats, void* stream,
-                 float* pz = nullptr, unsigned char* pa = nullptr, int pool_k = 0, const float* psign = nullptr);
+                 float* pz = nullptr, unsigned char* pa = nullptr, int pool_k = 0, const float* psign = nullptr,
+                 int bf16x3 = 0);
 // the 64 x 64 data gradient through an LDS-DMA ring (dgrad.hip): bitwise
 // gemm_rows_kernel<64, 64, 2, 2, PLAIN | BNBWD | POOLBWD, true, 0 | EPI_BWD> for the shapes dgrad_dma_ok accepts;
 // gx = the row blocks (= BN-backward partials per column)
@@ -222,6 +223,10 @@ int gemm_nt_bn(int N);                             // its column tile (128 or 25
 bool gemm_nt_ok(const float* A, int lda, const float* B, int ldb, int M, int N, int R);
 int gemm_nt(const float* A, int lda, const float* B, int ldb, int M, int N, int R, const float* bias, float* C, int ldc,
             double* stats, hipStream_t st);
+// the same product on the bf16 matrix pipe with split operands (gemm_big_bf16x3.hip); legal wherever
+// gemm_nt_ok holds (gemm_rows_ex takes it there when its bf16x3 argument is set)
+int gemm_nt_bf16x3(const float* A, int lda, const float* B, int ldb, int M, int N, int R, const float* bias, float* C,
+                   int ldc, double* stats, hipStream_t st);
 // wide weight gradient on plain operands (gemm_big.hip): partial tiles per row split
 bool wgrad_nt_ok(const float* X, int ldx, const float* Y, int ldy, int M, int N, int K);
 size_t wgrad_nt_ws_bytes(int N, int K, int M);

@@ -108,6 +108,7 @@ SIGNATURES = {
     'pcs_set_kernel_variant': [I32],
     'pcs_gemm_nt': [P, I32, P, I32, I32, I32, I32, P, P, I32, P, P],
     'pcs_gemm_nt_row_tiles': [I32],
+    'pcs_gemm_nt_bf16x3': [P, I32, P, I32, I32, I32, I32, P, P, I32, P, P],
     'pcs_wgrad_workspace': [I32, I32, I32, P],
     'pcs_wgrad': [OPP, I32, OPP, I32, I32, P, P, P, ctypes.c_size_t, P],
     'pcs_bn_finalize': [P, I32, I32, I64, P, P, F32, F32, P, P, P, P, P, P, P],

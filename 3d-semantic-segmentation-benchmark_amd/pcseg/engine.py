@@ -229,6 +229,8 @@ _inflight: dict = {}         # device index -> deque of join events
 inflight_wait_s = [0.0]      # host seconds spent in those waits (bench.py reports it apart)
 
 BWD_FUSE = {'default': 0, 'off': 1, 'all': 2}   # pcs_mlp_layer.bwd_fuse (include/pcseg.h)
+GEMM_BF16X3 = 0x100                             # PCS_GEMM_BF16X3: the wide-GEMM choice, above the fuse policy
+TRAIN_GEMM = ('fp32', 'bf16x3')
 
 
 def wgrad_lane(dev: torch.device):
@@ -292,6 +294,19 @@ def set_bwd_fuse(module: torch.nn.Module, policy: str = 'default') -> None:
     for m in module.modules():
         if hasattr(m, 'bwd_fuse'):
             m.bwd_fuse = v
+
+
+def set_train_gemm(module: torch.nn.Module, mode: str = 'bf16x3') -> None:
+    """Which kernel the wide training GEMMs under `module` run on (`train_gemm` of DGCNN / DGCNNWithColor,
+    the models with layers in the wide regime: conv5-7 over >= 65536 rows): 'fp32', the fp32 MFMA GEMM
+    (gemm_nt, the default), or 'bf16x3', the split-bf16 kernel (csrc/gemm_big_bf16x3.hip) for the forward
+    and the data gradient.  BatchNorm, dropout and the weight gradients are unchanged.  'bf16x3' agrees
+    with 'fp32' to ~5e-6 norm-relative per GEMM, not bitwise."""
+    if mode not in TRAIN_GEMM:
+        raise ValueError(f'train gemm must be one of {TRAIN_GEMM}, got {mode!r}')
+    for m in module.modules():
+        if hasattr(m, 'train_gemm'):
+            m.train_gemm = mode
 
 
 def set_edge_inverse(module: torch.nn.Module, where: str = 'side') -> None:
@@ -423,7 +438,7 @@ class SharedMLPFn(torch.autograd.Function):
         if cache is not None:
             # everything _layer_statics bakes into the records: parameter storage, the BN modes and
             # hyper-parameters, and the running-statistics buffers (pcseg.ddp.FlatBuffers rebinds them)
-            key = (Kin, acts, tuple(_nz(p) for p in params),
+            key = (Kin, acts, bwd_fuse, tuple(_nz(p) for p in params),
                    tuple((bn.training, bn.track_running_stats, bn.momentum, bn.eps, _nz(bn.running_mean),
                           _nz(bn.running_var), _nz(bn.num_batches_tracked)) for bn in bns))
             ent = cache.get('static')
@@ -904,7 +919,7 @@ def _rows_ok(x: torch.Tensor) -> bool:
 
 def shared_mlp(x_rows: torch.Tensor, kin: int, convs, bns, act='relu', slope=0.0,
                pool_k: int = 0, out: torch.Tensor | None = None, dropout: tuple | None = None,
-               bwd_fuse: int = 0, cache: dict | None = None, dx_from: int = 0) -> torch.Tensor:
+               bwd_fuse: int = 0, cache: dict | None = None, dx_from: int = 0, gemm: str = 'fp32') -> torch.Tensor:
     """Run a conv/BN/act stack on rows.  x_rows (M, W) with `kin` logical channels, W % 4 == 0,
     dense or a column block of a wider buffer (row stride >= W).  `act` / `slope` are one value
     for every layer or a sequence with one per layer ('relu', 'lrelu', 'none').  `out`: an
@@ -915,7 +930,10 @@ def shared_mlp(x_rows: torch.Tensor, kin: int, convs, bns, act='relu', slope=0.0
     `cache`: a dict owned by the calling module, where the stack's static layer records are
     kept between calls (host enqueue cost).  `dx_from`: the first input column whose gradient
     is wanted (pcs_mlp_layer.dx_col0): grouped rows start with 3 relative-coordinate columns
-    whose gradient no caller reads; the returned gradient's columns before it are undefined."""
+    whose gradient no caller reads; the returned gradient's columns before it are undefined.
+    `gemm`: 'bf16x3' sets PCS_GEMM_BF16X3 on the stack's records (TRAIN_GEMM, set_train_gemm)."""
+    if gemm not in TRAIN_GEMM:
+        raise ValueError(f'shared_mlp: gemm must be one of {TRAIN_GEMM}, got {gemm!r}')
     if not x_rows.is_cuda:
         raise RuntimeError('pcseg ops run only on the GPU (no CPU fallback); got a CPU tensor')
     if not _rows_ok(x_rows):
@@ -934,7 +952,7 @@ def shared_mlp(x_rows: torch.Tensor, kin: int, convs, bns, act='relu', slope=0.0
     if dropout is not None and (pool_k or not 0.0 < float(dropout[0]) < 1.0):
         raise ValueError('shared_mlp: dropout needs an un-pooled output and 0 < p < 1')
     return SharedMLPFn.apply(x_rows, kin, pool_k, acts, list(bns), None if out is None else (out,), dropout,
-                             int(bwd_fuse), cache, int(dx_from), *params)
+                             int(bwd_fuse) | (GEMM_BF16X3 if gemm == 'bf16x3' else 0), cache, int(dx_from), *params)
 
 
 class RowLinearFn(torch.autograd.Function):

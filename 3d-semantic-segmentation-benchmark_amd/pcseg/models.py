@@ -226,17 +226,18 @@ class PointNeXt(GeometryPrefetch, nn.Module):
 
 # ------------------------------------------------------------------------- DGCNN
 def _seq_rows(x_rows: torch.Tensor, seq: nn.Sequential, kin: int | None = None,
-              out: torch.Tensor | None = None, gemm: tuple = ('fp32', 0)) -> torch.Tensor:
+              out: torch.Tensor | None = None, gemm: tuple = ('fp32', 0), train_gemm: str = 'fp32') -> torch.Tensor:
     """Conv1d(bias=False) -> BN1d -> LeakyReLU [-> Dropout] on rows (HIP shared-MLP engine);
     `out`: a row block the activation is written into (no Dropout after it).  gemm: the model's
-    (eval_gemm, eval_gemm_rows) ('bf16x3': the split-bf16 kernel under eval() + no_grad)."""
+    (eval_gemm, eval_gemm_rows) ('bf16x3': the split-bf16 kernel under eval() + no_grad), which takes
+    precedence; train_gemm: the model's engine.set_train_gemm choice for the engine's wide GEMMs."""
     if _bf16x3(gemm, seq[0], seq[1], kin or x_rows.shape[1], x_rows.shape[0]):
         y = rows_infer(x_rows, kin or x_rows.shape[1], seq[0], seq[1], 'lrelu', seq[2].negative_slope, out=out)
         return seq[3](y) if len(seq) > 3 else y
     # training-mode Dropout fused into the stack's output
     drop = _fused_dropout(seq[3]) if len(seq) > 3 and out is None else None
     y = shared_mlp(x_rows, kin or x_rows.shape[1], [seq[0]], [seq[1]], 'lrelu', seq[2].negative_slope, 0, out=out,
-                   dropout=drop, cache=module_cache(seq))
+                   dropout=drop, cache=module_cache(seq), gemm=train_gemm)
     if len(seq) > 3 and drop is None:
         y = seq[3](y)
     return y
@@ -412,9 +413,10 @@ def _dgcnn_head(self, parts: list[torch.Tensor], B: int, N: int, H: torch.Tensor
         H = torch.empty((M, cxr + emb), dtype=torch.float32, device=parts[0].device)
     xr = _CopyColumns.apply((storage_alias(H, 0, cxr), (written,) * len(parts)), *parts)  # (B*N, 320|384), stride 1344|1408
     gemm = (self.eval_gemm, self.eval_gemm_rows)
-    x5 = _seq_rows(xr, self.conv5, out=storage_alias(H, cxr, emb), gemm=gemm)        # (B*N, emb)
-    x6 = _seq_rows(_ColumnConcat.apply(xr, x5), self.conv6, gemm=gemm)
-    x7 = _seq_rows(x6, self.conv7, gemm=gemm)
+    tg = self.train_gemm
+    x5 = _seq_rows(xr, self.conv5, out=storage_alias(H, cxr, emb), gemm=gemm, train_gemm=tg)   # (B*N, emb)
+    x6 = _seq_rows(_ColumnConcat.apply(xr, x5), self.conv6, gemm=gemm, train_gemm=tg)
+    x7 = _seq_rows(x6, self.conv7, gemm=gemm, train_gemm=tg)
     logits = _head_rows(x7, None, self.conv8, gemm).view(B, N, -1)
     # the reference returns x5 as a contiguous (B, emb, N); a transposed view of
     # the point-major rows has the same shape and values without a 0.5 GB copy
@@ -450,6 +452,7 @@ class DGCNN(nn.Module):
         self.conv7 = _head_seq(512, 256, dropout)
         self.conv8 = nn.Conv1d(256, num_classes, kernel_size=1)
         self.eval_gemm, self.eval_gemm_rows = 'fp32', 0     # pcseg.engine.set_eval_gemm: the head's GEMMs
+        self.train_gemm = 'fp32'                            # pcseg.engine.set_train_gemm: conv5-7 in training
 
     def forward(self, x):
         B, _, N = x.shape
@@ -486,6 +489,7 @@ class DGCNNWithColor(nn.Module):
         self.conv7 = _head_seq(512, 256, dropout)
         self.conv8 = nn.Conv1d(256, num_classes, kernel_size=1)
         self.eval_gemm, self.eval_gemm_rows = 'fp32', 0     # pcseg.engine.set_eval_gemm: the head's GEMMs
+        self.train_gemm = 'fp32'                            # pcseg.engine.set_train_gemm: conv5-7 in training
 
     def forward(self, x):
         if x.size(1) != 6:

@@ -235,6 +235,18 @@ int pcs_gemm_rows_kmajor_variant(const pcs_operand* a, int M, int K, const float
 int pcs_gemm_nt(const float* A, int lda, const float* B, int ldb, int M, int N, int R,
                 const float* bias, float* C, int ldc, double* stats, void* stream);
 int pcs_gemm_nt_row_tiles(int M);
+/* The same product on the bf16 matrix pipe (csrc/gemm_big_bf16x3.hip), for training:
+ * C (M x N, ldc) = A (M x R, lda) . B (N x R, ldb)^T (+ bias), fp32 storage on both
+ * sides.  Each operand is split x = hi + lo into two bf16 on its way into LDS and the
+ * product keeps hi.hi + hi.lo + lo.hi in one fp32 accumulator (about 16 significand
+ * bits per operand; ~4e-6 norm-relative against fp64, not bitwise pcs_gemm_nt).
+ * stats (nullable): pcs_gemm_nt's [2][N][pcs_gemm_nt_row_tiles(M)] fp64 partials of
+ * the valid rows.  A, B and C may be column blocks of wider buffers.  M >= 1; N >= 4
+ * and N % 4 == 0; R >= 32 and R % 32 == 0; lda, ldb, ldc multiples of 4 and >= R, R,
+ * N; A, B, C 16-B aligned.  Nothing is allocated.  The engine takes it instead of
+ * pcs_gemm_nt's kernel for the layers whose record carries PCS_GEMM_BF16X3. */
+int pcs_gemm_nt_bf16x3(const float* A, int lda, const float* B, int ldb, int M, int N, int R,
+                       const float* bias, float* C, int ldc, double* stats, void* stream);
 /* dW (N x K) += T(X)^T . T(Y) over M rows; db (N, nullable) += column sums of
  * T(X).  X: PLAIN/BNBWD/POOLBWD (the layer's dZ), Y: PLAIN/BNACT (its input).
  * (accumulating) Deterministic: each row split's partial tile is stored in the
@@ -329,6 +341,13 @@ typedef struct pcs_mlp_layer {
 #define PCS_BWD_FUSE_DEFAULT 0
 #define PCS_BWD_FUSE_OFF 1
 #define PCS_BWD_FUSE_ALL 2
+/* bwd_fuse also carries the layer's wide-GEMM choice above its low byte (the fuse policy):
+ * with PCS_GEMM_BF16X3 set, the forward GEMM and the first layer's data gradient that would
+ * run on pcs_gemm_nt's fp32 kernel (plain operands, M >= 65536, N >= 256) run on
+ * pcs_gemm_nt_bf16x3's split-bf16 kernel instead.  Everything else -- BatchNorm, dropout,
+ * the weight gradients -- is unchanged; without the bit nothing changes. */
+#define PCS_BWD_FUSE_MASK 0xff
+#define PCS_GEMM_BF16X3 0x100
 
 /* workspace bytes of pcs_mlp_forward (backward = 0) or pcs_mlp_backward (1) */
 int pcs_mlp_workspace(int M, int kin, int ldx, const pcs_mlp_layer* layers, int nl,
