@@ -143,6 +143,17 @@ static bool ring_wanted(int policy) { return policy == PCS_BWD_FUSE_ALL; }
 // the two halves of pcs_mlp_layer.bwd_fuse: the fuse policy (low byte) and the wide-GEMM choice
 static int fuse_policy(const pcs_mlp_layer& P) { return (int)(P.bwd_fuse & PCS_BWD_FUSE_MASK); }
 static int wide_bf16x3(const pcs_mlp_layer& P) { return (P.bwd_fuse & PCS_GEMM_BF16X3) ? 1 : 0; }
+static int wgrad_bf16x3_bit(const pcs_mlp_layer& P) { return (P.bwd_fuse & PCS_WGRAD_BF16X3) ? 1 : 0; }
+
+// partial-tile workspace of layer P's weight gradient over M rows: wgrad_launch's, and for a layer that
+// carries PCS_WGRAD_BF16X3 in the split-bf16 kernel's regime that kernel's as well (records without
+// the bit get the bytes they always got)
+static size_t layer_wgrad_ws(const pcs_mlp_layer& P, int M) {
+    size_t b = wgrad_ws_bytes((int)P.cout, (int)P.cin, M);
+    if (wgrad_bf16x3_bit(P) && M >= 65536 && P.cin % 4 == 0)
+        b = std::max(b, wgrad_bf16x3_ws_bytes((int)P.cout, (int)P.cin, M));
+    return b;
+}
 
 // Rotation depth of a backward's dA / kB / alpha buffers.  The dgrad of layer l reuses the buffers
 // that layer l + kRot - 1's wgrad reads, so it must wait for that wgrad on the lane; with kRot = 6 no
@@ -184,10 +195,10 @@ static size_t carve_backward(Carve& cv, int M, int kin, int ldx, const pcs_mlp_l
     for (int i = 0; i < kRot; ++i) s.dA[i] = i < std::max(1, std::min(nl - 1, kRot)) ? cv.take<float>(da) : nullptr;
     size_t wg = 0;
     for (int l = 0; l < nl; ++l)
-        if (L[l].dW) wg = std::max(wg, wgrad_ws_bytes((int)L[l].cout, (int)L[l].cin, M));
+        if (L[l].dW) wg = std::max(wg, layer_wgrad_ws(L[l], M));
     s.wg_bytes = wg;
     s.wg = cv.take<char>(wg);
-    s.wg0_bytes = L[0].dW ? wgrad_ws_bytes((int)L[0].cout, (int)L[0].cin, M) : 0;
+    s.wg0_bytes = L[0].dW ? layer_wgrad_ws(L[0], M) : 0;
     s.wg0 = cv.take<char>(s.wg0_bytes);
     size_t fw = 0;
     for (int l = 1; l < nl; ++l)
@@ -309,7 +320,7 @@ static int check_layers(int M, int kin, int ldx, const pcs_mlp_layer* L, int nl,
         PCS_CHECK_ARG(L[l].use_batch || (L[l].run_mean && L[l].run_var),
                       "%s: layer %d: eval-mode BatchNorm needs running statistics", who, l);
         PCS_CHECK_ARG(L[l].act >= 0 && L[l].act <= 2, "%s: layer %d: act=%lld", who, l, (long long)L[l].act);
-        PCS_CHECK_ARG((L[l].bwd_fuse & ~(int64_t)(PCS_BWD_FUSE_MASK | PCS_GEMM_BF16X3)) == 0 &&
+        PCS_CHECK_ARG((L[l].bwd_fuse & ~(int64_t)(PCS_BWD_FUSE_MASK | PCS_GEMM_BF16X3 | PCS_WGRAD_BF16X3)) == 0 &&
                           (L[l].bwd_fuse & PCS_BWD_FUSE_MASK) <= PCS_BWD_FUSE_ALL,
                       "%s: layer %d: bwd_fuse=%lld", who, l, (long long)L[l].bwd_fuse);
         cin = (int)L[l].cout;
@@ -523,7 +534,9 @@ static int mlp_backward(const float* X, int ldx, int kin, int M, const pcs_mlp_l
             if (int e = fused_wgrad(&xop, C, X, ldx, Cin, M, P.dW, P.db, S.fw, S.fw_bytes, st)) return fail(e);
         } else if (P.dW && wg_here) {
             const pcs_operand y = plain_op(X, ldx);
-            if (int e = pcs::wgrad_launch(&xop, C, &y, Cin, M, P.dW, P.db, S.wg0, S.wg0_bytes, stream)) return fail(e);
+            if (int e = pcs::wgrad_launch(&xop, C, &y, Cin, M, P.dW, P.db, S.wg0, S.wg0_bytes, stream,
+                                          wgrad_bf16x3_bit(P)))
+                return fail(e);
         } else if (P.dW) {
             void* ws_stream = stream;
             if (lane) {                    // fork: the side stream waits for dZ's inputs
@@ -534,7 +547,8 @@ static int mlp_backward(const float* X, int ldx, int kin, int M, const pcs_mlp_l
             }
             const pcs_mlp_layer* Q = l > 0 ? &layers[l - 1] : nullptr;
             const pcs_operand y = Q ? bnact_op(Q->Z, Cin, *Q) : plain_op(X, ldx);
-            const int e = pcs::wgrad_launch(&xop, C, &y, Cin, M, P.dW, P.db, S.wg, S.wg_bytes, ws_stream);
+            const int e = pcs::wgrad_launch(&xop, C, &y, Cin, M, P.dW, P.db, S.wg, S.wg_bytes, ws_stream,
+                                            wgrad_bf16x3_bit(P));
             if (lane) {                    // recorded even on error, so the join below covers it
                 pending = lane_event(lane);
                 (void)hipEventRecord(pending, lane->side);

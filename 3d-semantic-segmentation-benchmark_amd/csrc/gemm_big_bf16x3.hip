@@ -40,10 +40,6 @@
 
 namespace pcs {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int BX_BM = 256;               // rows of A per block tile (= gemm_nt's row tile: the stats layout)
 constexpr int BX_BN = 128;               // columns of C per block tile
 constexpr int BX_BK = 32;                // K slab: two MFMA K steps
@@ -51,25 +47,7 @@ constexpr int BX_LD = 2 * BX_BK + 8;     // bf16 per LDS row: [32 hi | 32 lo | 8
 constexpr int BX_STAGE = (BX_BM + BX_BN) * BX_LD;   // bf16 per stage: the A tile, then the B tile
 static_assert(2 * BX_STAGE * sizeof(__bf16) == 110592, "bf16x3 LDS budget");
 
-// two floats -> two bf16 (RNE) in one dword: v_cvt_pk_bf16_f32
-__device__ __forceinline__ unsigned bx_pk(float a, float b) {
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-
-// 8 consecutive K values -> their hi and lo units (8 bf16 = 16 B each)
-__device__ __forceinline__ void bx_split8(const float4 a, const float4 b, uint4& hi, uint4& lo) {
-    const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    unsigned h[4], l[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        h[p] = bx_pk(x[2 * p], x[2 * p + 1]);
-        // x - float(hi): exact (hi is x rounded to 8 significand bits)
-        l[p] = bx_pk(x[2 * p] - __uint_as_float(h[p] << 16), x[2 * p + 1] - __uint_as_float(h[p] & 0xffff0000u));
-    }
-    hi = make_uint4(h[0], h[1], h[2], h[3]);
-    lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
+// the operand split (bx_pk / bx_split8) and the bf16 vector types: mlp_common.hpp
 
 template <bool STATS>
 __global__ __launch_bounds__(512, 1) void gemm_nt_bf16x3_kernel(const float* __restrict__ A, int lda,

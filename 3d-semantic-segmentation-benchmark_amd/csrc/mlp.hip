@@ -1488,7 +1488,7 @@ size_t pcs::wgrad_ws_bytes(int N, int K, int M) {
 // dW (N x K) += T(X)^T . T(Y) over M rows; db (N) += column sums of T(X) (nullable).  Each row
 // split's partial goes to the workspace, then one reduce per output adds the splits in order.
 int pcs::wgrad_launch(const pcs_operand* x, int N, const pcs_operand* y, int K, int M, float* dW, float* db, void* ws,
-                      size_t ws_bytes, void* stream) {
+                      size_t ws_bytes, void* stream, int bf16x3) {
     PCS_CHECK_ARG(M >= 0 && N >= 1 && K >= 1, "pcs_wgrad: bad sizes");
     if (int e = check_operand(x, N, "pcs_wgrad", "X")) return e;
     if (int e = check_operand(y, K, "pcs_wgrad", "Y")) return e;
@@ -1496,6 +1496,11 @@ int pcs::wgrad_launch(const pcs_operand* x, int N, const pcs_operand* y, int K, 
     PCS_CHECK_ARG(y->mode <= PCS_OP_BNACT, "pcs_wgrad: Y operand must be PLAIN or BNACT");
     PCS_CHECK_ARG(dW && N % 4 == 0, "pcs_wgrad: dW null or N not a multiple of 4");
     if (M == 0) return 0;
+    // the layer's opt-in (PCS_WGRAD_BF16X3): a wide layer's materialised dZ and plain input on the
+    // split-bf16 kernel, with its own workspace size
+    if (bf16x3 && x->mode == PCS_OP_PLAIN && y->mode == PCS_OP_PLAIN && !db &&
+        wgrad_bf16x3_ok(x->data, x->ld, y->data, y->ld, M, N, K))
+        return wgrad_bf16x3(x->data, x->ld, y->data, y->ld, M, N, K, dW, ws, ws_bytes, as_stream(stream));
     const size_t need = wgrad_ws_bytes(N, K, M);
     PCS_CHECK_ARG(ws && ws_bytes >= need, "pcs_wgrad: workspace too small (%zu < %zu)", ws_bytes, need);
     float* part = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));

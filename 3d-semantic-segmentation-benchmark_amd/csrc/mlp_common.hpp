@@ -11,6 +11,31 @@ namespace pcs {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// ---- split-bf16 operands (gemm_big_bf16x3.hip, wgrad_bf16x3.hip): x = hi + lo, hi = bf16(x) (RNE)
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// two floats -> two bf16 (RNE) in one dword: v_cvt_pk_bf16_f32
+__device__ __forceinline__ unsigned bx_pk(float a, float b) {
+    const f32x2 v = {a, b};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+}
+
+// 8 consecutive K values -> their hi and lo units (8 bf16 = 16 B each)
+__device__ __forceinline__ void bx_split8(const float4 a, const float4 b, uint4& hi, uint4& lo) {
+    const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    unsigned h[4], l[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        h[p] = bx_pk(x[2 * p], x[2 * p + 1]);
+        // x - float(hi): exact (hi is x rounded to 8 significand bits)
+        l[p] = bx_pk(x[2 * p] - __uint_as_float(h[p] << 16), x[2 * p + 1] - __uint_as_float(h[p] & 0xffff0000u));
+    }
+    hi = make_uint4(h[0], h[1], h[2], h[3]);
+    lo = make_uint4(l[0], l[1], l[2], l[3]);
+}
+
 enum { ACT_RELU = 0, ACT_LRELU = 1, ACT_NONE = 2 };
 
 // The activation is folded into one slope at the ABI boundary (eff_slope): ReLU = 0,
@@ -232,6 +257,12 @@ bool wgrad_nt_ok(const float* X, int ldx, const float* Y, int ldy, int M, int N,
 size_t wgrad_nt_ws_bytes(int N, int K, int M);
 int wgrad_nt(const float* X, int ldx, const float* Y, int ldy, int M, int N, int K, float* part, hipStream_t st);
 const char* wgrad_nt_name(int N, int K, int M);
+// the wide weight gradient on the bf16 matrix pipe with split operands (wgrad_bf16x3.hip): dW (N x K) +=
+// X^T . Y through per-split partial tiles in ws; _ok = the engine's predicate (alignment, M >= 65536)
+bool wgrad_bf16x3_ok(const float* X, int ldx, const float* Y, int ldy, int M, int N, int K);
+size_t wgrad_bf16x3_ws_bytes(int N, int K, int M);
+int wgrad_bf16x3(const float* X, int ldx, const float* Y, int ldy, int M, int N, int K, float* dW, void* ws,
+                 size_t ws_bytes, hipStream_t st);
 // pooled output of a stack from the GEMM's fused z-space extreme (pz/pa of gemm_rows_ex): out =
 // act(s*z + t) with z = the max of the group where gamma >= 0, its min where gamma < 0 (the one
 // extreme the producer kept per channel; s = gamma * invstd with invstd > 0, so the signs agree)
@@ -243,9 +274,11 @@ int pool_finalize(const float* pz, const unsigned char* pa, long long G, int N, 
                   int ld2 = 0);
 // engine launch probe: probe_enabled / probe_start / probe_stop (pcs_common.hpp, probe.cpp)
 // weight gradient with deterministic partials: workspace bytes for (N, K, M), and the launch
+// (bf16x3: the layer's PCS_WGRAD_BF16X3 -- plain operands in wgrad_bf16x3_ok's regime without a bias
+// gradient take wgrad_bf16x3, whose workspace is wgrad_bf16x3_ws_bytes)
 size_t wgrad_ws_bytes(int N, int K, int M);
 int wgrad_launch(const pcs_operand* x, int N, const pcs_operand* y, int K, int M, float* dW, float* db, void* ws,
-                 size_t ws_bytes, void* stream);
+                 size_t ws_bytes, void* stream, int bf16x3 = 0);
 
 // device-side operand of an ABI operand (the activation folded into one slope) over rows x cols
 // (its extent, for the debug library's bounds checks)

@@ -111,6 +111,8 @@ SIGNATURES = {
     'pcs_gemm_nt_bf16x3': [P, I32, P, I32, I32, I32, I32, P, P, I32, P, P],
     'pcs_wgrad_workspace': [I32, I32, I32, P],
     'pcs_wgrad': [OPP, I32, OPP, I32, I32, P, P, P, ctypes.c_size_t, P],
+    'pcs_wgrad_bf16x3_workspace': [I32, I32, I32, P],
+    'pcs_wgrad_bf16x3': [P, I32, P, I32, I32, I32, I32, P, P, ctypes.c_size_t, P],
     'pcs_bn_finalize': [P, I32, I32, I64, P, P, F32, F32, P, P, P, P, P, P, P],
     'pcs_bn_bwd_finalize': [P, I32, I32, I64, P, P, P, P, P, P, I32, P],
     'pcs_bn_bwd_reduce_blocks': [I32],

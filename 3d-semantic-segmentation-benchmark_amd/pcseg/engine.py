@@ -230,7 +230,9 @@ inflight_wait_s = [0.0]      # host seconds spent in those waits (bench.py repor
 
 BWD_FUSE = {'default': 0, 'off': 1, 'all': 2}   # pcs_mlp_layer.bwd_fuse (include/pcseg.h)
 GEMM_BF16X3 = 0x100                             # PCS_GEMM_BF16X3: the wide-GEMM choice, above the fuse policy
-TRAIN_GEMM = ('fp32', 'bf16x3')
+WGRAD_BF16X3 = 0x200                            # PCS_WGRAD_BF16X3: the wide weight gradient's, beside it
+TRAIN_GEMM = ('fp32', 'bf16x3', 'bf16x3+wgrad')
+_TRAIN_GEMM_BITS = {'fp32': 0, 'bf16x3': GEMM_BF16X3, 'bf16x3+wgrad': GEMM_BF16X3 | WGRAD_BF16X3}
 
 
 def wgrad_lane(dev: torch.device):
@@ -299,9 +301,10 @@ def set_bwd_fuse(module: torch.nn.Module, policy: str = 'default') -> None:
 def set_train_gemm(module: torch.nn.Module, mode: str = 'bf16x3') -> None:
     """Which kernel the wide training GEMMs under `module` run on (`train_gemm` of DGCNN / DGCNNWithColor,
     the models with layers in the wide regime: conv5-7 over >= 65536 rows): 'fp32', the fp32 MFMA GEMM
-    (gemm_nt, the default), or 'bf16x3', the split-bf16 kernel (csrc/gemm_big_bf16x3.hip) for the forward
-    and the data gradient.  BatchNorm, dropout and the weight gradients are unchanged.  'bf16x3' agrees
-    with 'fp32' to ~5e-6 norm-relative per GEMM, not bitwise."""
+    (gemm_nt, the default), 'bf16x3', the split-bf16 kernel (csrc/gemm_big_bf16x3.hip) for the forward
+    and the data gradient with the weight gradients unchanged, or 'bf16x3+wgrad', which also runs the wide
+    weight gradients on their split-bf16 kernel (csrc/wgrad_bf16x3.hip).  BatchNorm and dropout are
+    unchanged.  The split-bf16 modes agree with 'fp32' to ~5e-6 norm-relative per GEMM, not bitwise."""
     if mode not in TRAIN_GEMM:
         raise ValueError(f'train gemm must be one of {TRAIN_GEMM}, got {mode!r}')
     for m in module.modules():
@@ -525,7 +528,8 @@ class SharedMLPFn(torch.autograd.Function):
         dX = None
         if ctx.needs_input_grad[0]:
             dX = _f32((M, X.shape[1]), dev)       # dense, X's width (its pad columns zeroed)
-        key = (M, Kin, ldx, tuple(couts), pool_K, 1, dp > 0.0)
+        # (records that carry PCS_WGRAD_BF16X3 size the weight gradient's partial tiles for its kernel)
+        key = (M, Kin, ldx, tuple(couts), pool_K, 1, dp > 0.0, bool(ctx.bwd_fuse & WGRAD_BF16X3))
         nws = _workspace(lib, key, M, Kin, ldx, recs, nl, pool_K, 1)
         ws = torch.empty((nws,), dtype=torch.uint8, device=dev)
         lane = wgrad_lane(dev)
@@ -931,7 +935,8 @@ def shared_mlp(x_rows: torch.Tensor, kin: int, convs, bns, act='relu', slope=0.0
     kept between calls (host enqueue cost).  `dx_from`: the first input column whose gradient
     is wanted (pcs_mlp_layer.dx_col0): grouped rows start with 3 relative-coordinate columns
     whose gradient no caller reads; the returned gradient's columns before it are undefined.
-    `gemm`: 'bf16x3' sets PCS_GEMM_BF16X3 on the stack's records (TRAIN_GEMM, set_train_gemm)."""
+    `gemm`: 'bf16x3' sets PCS_GEMM_BF16X3 on the stack's records, 'bf16x3+wgrad' PCS_WGRAD_BF16X3 as well
+    (TRAIN_GEMM, set_train_gemm)."""
     if gemm not in TRAIN_GEMM:
         raise ValueError(f'shared_mlp: gemm must be one of {TRAIN_GEMM}, got {gemm!r}')
     if not x_rows.is_cuda:
@@ -952,7 +957,7 @@ def shared_mlp(x_rows: torch.Tensor, kin: int, convs, bns, act='relu', slope=0.0
     if dropout is not None and (pool_k or not 0.0 < float(dropout[0]) < 1.0):
         raise ValueError('shared_mlp: dropout needs an un-pooled output and 0 < p < 1')
     return SharedMLPFn.apply(x_rows, kin, pool_k, acts, list(bns), None if out is None else (out,), dropout,
-                             int(bwd_fuse) | (GEMM_BF16X3 if gemm == 'bf16x3' else 0), cache, int(dx_from), *params)
+                             int(bwd_fuse) | _TRAIN_GEMM_BITS[gemm], cache, int(dx_from), *params)
 
 
 class RowLinearFn(torch.autograd.Function):

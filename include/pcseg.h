@@ -77,7 +77,7 @@ int pcs_knn_seeded(const float* x, int B, int N, int F, int k, const int32_t* se
                    int ks, int32_t* out_idx, void* ws, size_t ws_bytes, void* stream);
 /* Morton order (B,N) int32 of each cloud's points by their first three features (x (B,N,F),
  * F >= 3: DGCNN's xyz, dgcnn.py:183 / :228 graph input); clouds past 8192 points get the
- * identity order.  Computed once per forward and shared by its four graphs. */
+ * identity order.  Computed once per forward and shared by its graphs 1-3. */
 int pcs_knn_order(const float* x, int B, int N, int F, int32_t* order, void* stream);
 /* pcs_knn_seeded (seeds nullable) scanning each cloud in `order` (a permutation of 0..N-1 per
  * cloud, pcs_knn_order's output) nearest tiles first, skipping the candidate tiles that are
@@ -256,6 +256,20 @@ int pcs_gemm_nt_bf16x3(const float* A, int lda, const float* B, int ldb, int M, 
 int pcs_wgrad_workspace(int N, int K, int M, size_t* bytes);
 int pcs_wgrad(const pcs_operand* x, int N, const pcs_operand* y, int K, int M,
               float* dW, float* db, void* workspace, size_t ws_bytes, void* stream);
+/* The wide weight gradient on the bf16 matrix pipe (csrc/wgrad_bf16x3.hip), for training:
+ * dW (N x K, contiguous; accumulating) += X (M x N, ldx)^T . Y (M x K, ldy), fp32 storage
+ * on both sides, X a layer's materialised dZ and Y its plain input.  pcs_gemm_nt_bf16x3's
+ * arithmetic: each operand is split x = hi + lo into two bf16 on its way into LDS (here
+ * transposed, the contraction runs over rows) and a product keeps hi.hi + hi.lo + lo.hi in
+ * one fp32 accumulator (~4e-6 norm-relative against fp64, not bitwise pcs_wgrad).
+ * Deterministic as pcs_wgrad: per-split partial tiles in the workspace
+ * (pcs_wgrad_bf16x3_workspace bytes, in use until the call's work on `stream` completes),
+ * added in split order.  X and Y may be column blocks of wider buffers.  M >= 1; N, K >= 4
+ * and multiples of 4; ldx, ldy multiples of 4 and >= N, K; X, Y 16-B aligned.  Nothing is
+ * allocated.  The engine takes it for the layers whose record carries PCS_WGRAD_BF16X3. */
+int pcs_wgrad_bf16x3_workspace(int N, int K, int M, size_t* bytes);
+int pcs_wgrad_bf16x3(const float* X, int ldx, const float* Y, int ldy, int M, int N, int K,
+                     float* dW, void* workspace, size_t ws_bytes, void* stream);
 /* BN forward finalize: partials -> scale s, shift t, mean, invstd; running
  * mean/var updated with `momentum` and the unbiased variance (nullable). */
 int pcs_bn_finalize(const double* part, int nb, int N, long long M,
@@ -345,9 +359,15 @@ typedef struct pcs_mlp_layer {
  * with PCS_GEMM_BF16X3 set, the forward GEMM and the first layer's data gradient that would
  * run on pcs_gemm_nt's fp32 kernel (plain operands, M >= 65536, N >= 256) run on
  * pcs_gemm_nt_bf16x3's split-bf16 kernel instead.  Everything else -- BatchNorm, dropout,
- * the weight gradients -- is unchanged; without the bit nothing changes. */
+ * the weight gradients -- is unchanged; without the bit nothing changes.
+ * With PCS_WGRAD_BF16X3 set, the layer's weight gradient runs on pcs_wgrad_bf16x3's
+ * split-bf16 kernel where both of its operands are plain (the layer's dZ was materialised
+ * and its input is the stack's input X), no bias gradient is wanted and M >= 65536, on the
+ * stream it runs on anyway; every other weight gradient is unchanged, and the backward
+ * workspace grows only for records that carry the bit.  The two bits are independent. */
 #define PCS_BWD_FUSE_MASK 0xff
 #define PCS_GEMM_BF16X3 0x100
+#define PCS_WGRAD_BF16X3 0x200
 
 /* workspace bytes of pcs_mlp_forward (backward = 0) or pcs_mlp_backward (1) */
 int pcs_mlp_workspace(int M, int kin, int ldx, const pcs_mlp_layer* layers, int nl,
