@@ -713,8 +713,9 @@ def edgeconv_infer(x_rows: torch.Tensor, cin: int, idx: torch.Tensor, conv, bn, 
 
 def set_eval_fuse(module: torch.nn.Module, on: bool = True) -> None:
     """Let every MiniPointNet under `module` run its grouped, max-pooled stack through the fused
-    eval-mode kernel (group_mlp_infer) whenever BatchNorm is in eval mode, grad is disabled and the
-    shape is covered (group_mlp_infer_ok).  Off by default: the folded-weight kernel agrees with the
+    eval-mode kernel (group_mlp_infer), and every TNet / PointNetEncoder its stack pooled over the cloud
+    (cloud_mlp_infer), whenever BatchNorm is in eval mode, grad is disabled and the shape is covered
+    (group_mlp_infer_ok, cloud_mlp_infer_ok).  Off by default: the folded-weight kernels agree with the
     layered path to fp32 rounding, not bitwise."""
     for m in module.modules():
         if hasattr(m, 'eval_fuse'):
@@ -770,6 +771,74 @@ def group_mlp_infer(xyz: torch.Tensor, feats: torch.Tensor, cent: torch.Tensor, 
     out = _f32((B * C, couts[-1]), dev)
     call('pcs_group_mlp_infer', ptr(xyz), ptr(feats), ptr(cent), ptr(idx), B, N, C, K, D, float(r),
          int(bool(normalize)), recs, len(convs), ptr(out), stream_ptr(dev))
+    return out
+
+
+def cloud_mlp_infer_ok(convs, bns, kin: int, acts) -> bool:
+    """The fused eval-mode per-cloud stack (csrc/cloud_mlp_infer.hip) covers 2 or 3 layers on 4 <= kin <= 128
+    channels: ReLU layers of width % 4 == 0 up to 128, then a last layer of a width that is a multiple of
+    128 with a ReLU or no activation, every BatchNorm on its running statistics, and stacks that fit one
+    CU's LDS (pcs_cloud_mlp_infer_workspace, the only holder of these limits)."""
+    nl = len(convs)
+    if not (nl in (2, 3) and len(bns) == nl and len(acts) == nl):
+        return False
+    for bn in bns:
+        if (bn.training or bn.running_mean is None or bn.running_var is None or bn.weight is None
+                or bn.bias is None):
+            return False
+    widths = tuple(int(c.weight.shape[0]) for c in convs)
+    key = ('cmi', int(kin), widths, tuple(acts))
+    ok = _ws_cache.get(key)
+    if ok is None:
+        ok = all(a in ACT for a in acts)
+        if ok:          # sizes only: the records carry non-null placeholder pointers
+            recs, cin = [], int(kin)
+            for C, a in zip(widths, acts):
+                recs.append(_REC.pack(16, ld4(cin), cin, C, 0, 16, 16, 16, 16, 0, 0.0, 1e-5, 0, ACT[a], 0.0,
+                                      0, 0, 0, 0, 0, 0, 0.0, 0, 0, 0))
+                cin = C
+            ok = load().pcs_cloud_mlp_infer_workspace(1, 1, b''.join(recs), nl, ctypes.byref(ctypes.c_size_t(0))) == 0
+        _ws_cache[key] = ok
+    return ok
+
+
+def cloud_mlp_infer(x_rows: torch.Tensor, kin: int, B: int, N: int, convs, bns, acts) -> torch.Tensor:
+    """Eval-mode conv + BN (+ ReLU) stack max-pooled over each cloud, outside autograd (TNet / PointNetEncoder,
+    PointNet.py:23-27, 80-85 under model.eval()): x_rows (B*N, ld) with kin channels, cloud b = rows
+    b N .. b N + N - 1; acts: one of 'relu' / 'none' per layer -> (B, cout_L) = act(max over the cloud's
+    points of BN(conv(..relu(BN(conv(x)))..))) in one pass (pcs_cloud_mlp_infer): the (B*N, cout_L)
+    activation is never written.  Nothing is saved, recorded or updated."""
+    if not x_rows.is_cuda:
+        raise RuntimeError('pcseg ops run only on the GPU (no CPU fallback); got a CPU tensor')
+    acts = tuple(acts)
+    if not cloud_mlp_infer_ok(convs, bns, kin, acts):
+        raise ValueError('cloud_mlp_infer: needs eval-mode BatchNorm with running statistics, 2 or 3 layers on '
+                         '4 <= kin <= 128 channels, ReLU layers of width % 4 == 0 <= 128, then a last layer of a '
+                         'multiple of 128 channels with ReLU or no activation, and a stack that fits the LDS')
+    x_rows = x_rows.detach()
+    if x_rows.dim() != 2 or x_rows.shape[0] != B * N or B < 1 or N < 1:
+        raise ValueError(f'cloud_mlp_infer: x_rows must be ({B} * {N}, ld) rows')
+    if not _rows_ok(x_rows) or x_rows.shape[1] < kin:
+        x_rows = pad_rows(x_rows[:, :kin])
+    dev = x_rows.device
+    params = []
+    for conv, bn in zip(convs, bns):
+        params += [conv.weight, conv.bias, bn.weight, bn.bias]
+    couts = [c.weight.shape[0] for c in convs]
+    statics, Wms, _ = _layer_statics(kin, bns, tuple((ACT[a], 0.0) for a in acts), params, couts, dev)
+    if Wms[-1].data_ptr() % 16:
+        raise ValueError('cloud_mlp_infer: the last weight must be 16-B aligned')
+    recs = b''.join(s + _DYN.pack(0, 0, 0, 0, 0, 0, 0.0, 0, 0, 0) for s in statics)
+    key = ('cmi_ws', B, N, couts[-1])
+    nws = _ws_cache.get(key)
+    if nws is None:
+        n = ctypes.c_size_t(0)
+        call('pcs_cloud_mlp_infer_workspace', B, N, recs, len(convs), ctypes.byref(n))
+        nws = _ws_cache[key] = int(n.value)
+    ws = _f32((nws // 4,), dev)
+    out = _f32((B, couts[-1]), dev)
+    call('pcs_cloud_mlp_infer', ptr(x_rows), x_rows.stride(0), kin, B, N, recs, len(convs), ptr(out), ptr(ws), nws,
+         stream_ptr(dev))
     return out
 
 

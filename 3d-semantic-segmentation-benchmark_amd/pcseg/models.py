@@ -18,7 +18,8 @@ import torch.nn.functional as F
 from . import ops
 from .common import SetAbstraction, FeaturePropagation, InvResMLP, UnitPointNet, GeometryPlan, GeometryPrefetch
 from .engine import (shared_mlp, pad_rows, linear_rows, edgeconv, edgeconv_fused_ok, edgeconv_infer, edgeconv_infer_ok,
-                     group_mlp_infer, storage_alias, module_cache, EdgeInverseBatch, rows_infer, rows_infer_ok)
+                     group_mlp_infer, storage_alias, module_cache, EdgeInverseBatch, rows_infer, rows_infer_ok,
+                     cloud_mlp_infer, cloud_mlp_infer_ok)
 from .replay import active as _replay
 from ._lib import call, ptr, stream_ptr
 
@@ -544,13 +545,18 @@ class TNet(nn.Module):
         self.bn3 = nn.BatchNorm1d(1024)
         self.bn4 = nn.BatchNorm1d(512)
         self.bn5 = nn.BatchNorm1d(256)
+        self.eval_fuse = False      # fused eval-mode stack + per-cloud max kernel (pcseg.engine.set_eval_fuse)
 
     def forward_points(self, xp):
         """xp (B, N, k) point-major."""
         B, N, _ = xp.shape
         r = pad_rows(xp.reshape(B * N, -1))
-        r = shared_mlp(r, self.k, [self.conv1, self.conv2, self.conv3], [self.bn1, self.bn2, self.bn3], 'relu')
-        g = r.view(B, N, -1).max(dim=1)[0]
+        convs, bns, acts = [self.conv1, self.conv2, self.conv3], [self.bn1, self.bn2, self.bn3], ('relu',) * 3
+        if self.eval_fuse and not torch.is_grad_enabled() and cloud_mlp_infer_ok(convs, bns, self.k, acts):
+            g = cloud_mlp_infer(r, self.k, B, N, convs, bns, acts)
+        else:
+            r = shared_mlp(r, self.k, convs, bns, 'relu')
+            g = r.view(B, N, -1).max(dim=1)[0]
         g = F.relu(self.bn4(self.fc1(g)))
         g = F.relu(self.bn5(self.fc2(g)))
         eye = torch.eye(self.k, device=g.device).view(1, self.k * self.k).repeat(B, 1)
@@ -576,6 +582,7 @@ class PointNetEncoder(nn.Module):
         self.conv3 = nn.Conv1d(128, 1024, 1)
         self.bn3 = nn.BatchNorm1d(1024)
         self.global_feat = global_feat
+        self.eval_fuse = False      # fused eval-mode stack + per-cloud max kernel (pcseg.engine.set_eval_fuse)
 
     def forward_points(self, xp):
         B, N, _ = xp.shape
@@ -588,8 +595,12 @@ class PointNetEncoder(nn.Module):
             r = torch.bmm(r.view(B, N, -1), trans_feat).reshape(B * N, -1)
         pf = r.view(B, N, -1)
         # conv2 -> BN -> ReLU -> conv3 -> BN (no activation, PointNet.py:82-83) in one engine stack
-        r = shared_mlp(r, 64, [self.conv2, self.conv3], [self.bn2, self.bn3], ('relu', 'none'))
-        g = r.view(B, N, -1).max(dim=1)[0]
+        convs, bns, acts = [self.conv2, self.conv3], [self.bn2, self.bn3], ('relu', 'none')
+        if self.eval_fuse and not torch.is_grad_enabled() and cloud_mlp_infer_ok(convs, bns, 64, acts):
+            g = cloud_mlp_infer(r, 64, B, N, convs, bns, acts)
+        else:
+            r = shared_mlp(r, 64, convs, bns, acts)
+            g = r.view(B, N, -1).max(dim=1)[0]
         if self.global_feat:
             return g, trans, trans_feat
         return torch.cat([g.view(B, 1, 1024).expand(B, N, 1024), pf], dim=2), trans, trans_feat

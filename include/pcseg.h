@@ -421,6 +421,22 @@ int pcs_group_mlp_infer(const float* xyz, const float* feats, const float* cent,
  * % 4 == 0; X, W, Y 16-B aligned; act 0 / 1 (slope >= 0) / 2.  Nothing is allocated. */
 int pcs_rows_infer(const float* X, int ldx, long long M, const pcs_mlp_layer* layer, float* Y,
                    int ldy, void* stream);
+/* Eval-mode PointNet stack max-pooled over each cloud in one pass (TNet, PointNet.py:23-27, and
+ * PointNetEncoder, PointNet.py:80-85, under model.eval()): X (B*N rows of kin channels, row stride
+ * ldx; cloud b = rows b N .. b N + N - 1) -> nl - 1 thin layers relu(BN(conv)) on the fp32 matrix
+ * pipe out of LDS -> the wide last layer BN(conv) on the bf16 pipe with pcs_rows_infer's split
+ * arithmetic -> max over the cloud's N rows -> ReLU or nothing -> out (B x cout_nl).  BatchNorm on
+ * its running statistics is folded into every conv on the device; only per-tile column maxima
+ * (the workspace) and out are written.  layers: fields W .. slope of each record (bias nullable;
+ * use_batch must be 0; act ReLU, the last layer's ReLU or none; Z, coef and the gradients are not
+ * read; W and the running statistics are only read).  nl 2 or 3; kin = layers[0].cin 4 .. 128,
+ * ldx % 4 == 0 and >= kin, X 16-B aligned; thin widths % 4 == 0, 4 .. 128; the last width a
+ * multiple of 128, its W 16-B aligned with ldw % 4 == 0; the stack must fit one CU's LDS.
+ * pcs_cloud_mlp_infer_workspace returns the workspace bytes, or non-zero (with a message) when
+ * the stack is not covered.  Nothing is allocated; both launches are deterministic. */
+int pcs_cloud_mlp_infer_workspace(int B, int N, const pcs_mlp_layer* layers, int nl, size_t* bytes);
+int pcs_cloud_mlp_infer(const float* X, int ldx, int kin, int B, int N, const pcs_mlp_layer* layers,
+                        int nl, float* out, void* ws, size_t ws_bytes, void* stream);
 /* the current device's wgrad lane stream (null if none could be created) */
 int pcs_wgrad_lane(void** side_stream);
 /* `stream` waits for every weight gradient enqueued on the current device's lane so far */
