@@ -714,9 +714,11 @@ def edgeconv_infer(x_rows: torch.Tensor, cin: int, idx: torch.Tensor, conv, bn, 
 def set_eval_fuse(module: torch.nn.Module, on: bool = True) -> None:
     """Let every MiniPointNet under `module` run its grouped, max-pooled stack through the fused
     eval-mode kernel (group_mlp_infer), and every TNet / PointNetEncoder its stack pooled over the cloud
-    (cloud_mlp_infer), whenever BatchNorm is in eval mode, grad is disabled and the shape is covered
-    (group_mlp_infer_ok, cloud_mlp_infer_ok).  Off by default: the folded-weight kernels agree with the
-    layered path to fp32 rounding, not bitwise."""
+    (cloud_mlp_infer), and every PointNetSeg its segmentation head -- conv1 .. conv4 and the softmax on the
+    pooled vector and the point rows, without the concatenation (point_head_infer) -- whenever BatchNorm is
+    in eval mode, grad is disabled and the shape is covered (group_mlp_infer_ok, cloud_mlp_infer_ok,
+    point_head_infer_ok).  Off by default: the folded-weight kernels agree with the layered path to fp32
+    rounding, not bitwise."""
     for m in module.modules():
         if hasattr(m, 'eval_fuse'):
             m.eval_fuse = bool(on)
@@ -839,6 +841,90 @@ def cloud_mlp_infer(x_rows: torch.Tensor, kin: int, B: int, N: int, convs, bns, 
     out = _f32((B, couts[-1]), dev)
     call('pcs_cloud_mlp_infer', ptr(x_rows), x_rows.stride(0), kin, B, N, recs, len(convs), ptr(out), ptr(ws), nws,
          stream_ptr(dev))
+    return out
+
+
+def _head_record(W, ldw: int, cin: int, classes: int, bias) -> bytes:
+    """The classifier's pcs_mlp_layer record: bias only (no BatchNorm pointers), no activation."""
+    return _REC.pack(W, ldw, cin, classes, bias, 0, 0, 0, 0, 0, 0.0, 0.0, 0, ACT['none'], 0.0,
+                     0, 0, 0, 0, 0, 0, 0.0, 0, 0, 0)
+
+
+def point_head_infer_ok(convs, bns, kg: int, kp: int) -> bool:
+    """The fused eval-mode PointNet segmentation head (csrc/point_head_infer.hip) covers four 1x1 convs on
+    kg pooled + kp point channels (kg % 4 == 0; kp % 4 == 0, 4 .. 128): three of widths 512, 256, 128 with a
+    BatchNorm on its running statistics and a ReLU each, then a bias-only classifier of 1 .. 32 classes
+    (pcs_point_head_infer_workspace, the only holder of these limits)."""
+    if not (len(convs) == 4 and len(bns) == 3):
+        return False
+    for bn in bns:
+        if (bn.training or bn.running_mean is None or bn.running_var is None or bn.weight is None
+                or bn.bias is None):
+            return False
+    widths = tuple(int(c.weight.shape[0]) for c in convs)
+    key = ('phi', int(kg), int(kp), widths)
+    ok = _ws_cache.get(key)
+    if ok is None:      # sizes only: the records carry non-null placeholder pointers
+        recs, cin = [], int(kg) + int(kp)
+        for C in widths[:3]:
+            recs.append(_REC.pack(16, ld4(cin), cin, C, 0, 16, 16, 16, 16, 0, 0.0, 1e-5, 0, ACT['relu'], 0.0,
+                                  0, 0, 0, 0, 0, 0, 0.0, 0, 0, 0))
+            cin = C
+        recs.append(_head_record(16, ld4(cin), cin, widths[3], 0))
+        ok = _ws_cache[key] = load().pcs_point_head_infer_workspace(1, 1, int(kg), b''.join(recs), 4,
+                                                                    ctypes.byref(ctypes.c_size_t(0))) == 0
+    return ok
+
+
+def point_head_infer(p_rows: torch.Tensor, kp: int, g: torch.Tensor, B: int, N: int, convs, bns,
+                     softmax: bool = True) -> torch.Tensor:
+    """Eval-mode PointNet segmentation head outside autograd (PointNet.py:86-90, 140-149 under model.eval()):
+    p_rows (B*N, ld) with kp point channels, cloud b = rows b N .. b N + N - 1, and the pooled g (B, kg) ->
+    (B*N, classes) = conv4(relu(BN(conv3(relu(BN(conv2(relu(BN(conv1([g_b | p]))))))))), with exp / sum over
+    the classes when `softmax`, in one pass (pcs_point_head_infer): conv1's columns on g become a per-cloud
+    bias, so neither the (B*N, kg + kp) concatenation nor any hidden activation is written.  Nothing is saved,
+    recorded or updated."""
+    if not (p_rows.is_cuda and g.is_cuda):
+        raise RuntimeError('pcseg ops run only on the GPU (no CPU fallback); got a CPU tensor')
+    g = g.detach().float()
+    if g.dim() != 2 or g.shape[0] != B:
+        raise ValueError(f'point_head_infer: g must be ({B}, kg)')
+    kg = int(g.shape[1])
+    if not point_head_infer_ok(convs, bns, kg, kp):
+        raise ValueError('point_head_infer: needs eval-mode BatchNorm with running statistics on three layers of '
+                         'widths 512, 256, 128, a bias-only classifier of 1 .. 32 classes, kg % 4 == 0 and '
+                         'kp % 4 == 0 in 4 .. 128')
+    p_rows = p_rows.detach()
+    if p_rows.dim() != 2 or p_rows.shape[0] != B * N or B < 1 or N < 1:
+        raise ValueError(f'point_head_infer: p_rows must be ({B} * {N}, ld) rows')
+    if not _rows_ok(p_rows) or p_rows.shape[1] < kp:
+        p_rows = pad_rows(p_rows[:, :kp])
+    if not _rows_ok(g):
+        g = pad_rows(g)
+    dev = p_rows.device
+    params = []
+    for conv, bn in zip(convs, bns):
+        params += [conv.weight, conv.bias, bn.weight, bn.bias]
+    couts = [c.weight.shape[0] for c in convs]
+    statics, Wms, _ = _layer_statics(kg + kp, bns, ((ACT['relu'], 0.0),) * 3, params, couts[:3], dev)
+    W4 = convs[3].weight.detach().reshape(couts[3], -1)
+    if not _rows_ok(W4):
+        W4 = pad_rows(W4)
+    Wms.append(W4)
+    if any(W.data_ptr() % 16 for W in Wms):
+        raise ValueError('point_head_infer: the weights must be 16-B aligned')
+    recs = b''.join(s + _DYN.pack(0, 0, 0, 0, 0, 0, 0.0, 0, 0, 0) for s in statics)
+    recs += _head_record(W4.data_ptr(), W4.stride(0), couts[2], couts[3], _nz(convs[3].bias))
+    key = ('phi_ws', B, N, kg, kp, couts[3])
+    nws = _ws_cache.get(key)
+    if nws is None:
+        n = ctypes.c_size_t(0)
+        call('pcs_point_head_infer_workspace', B, N, kg, recs, 4, ctypes.byref(n))
+        nws = _ws_cache[key] = int(n.value)
+    ws = _f32((nws // 4,), dev)
+    out = _f32((B * N, couts[3]), dev)
+    call('pcs_point_head_infer', ptr(p_rows), p_rows.stride(0), ptr(g), g.stride(0), kg, B, N, recs, 4,
+         int(bool(softmax)), ptr(out), out.stride(0), ptr(ws), nws, stream_ptr(dev))
     return out
 
 

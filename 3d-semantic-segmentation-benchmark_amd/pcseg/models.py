@@ -19,7 +19,7 @@ from . import ops
 from .common import SetAbstraction, FeaturePropagation, InvResMLP, UnitPointNet, GeometryPlan, GeometryPrefetch
 from .engine import (shared_mlp, pad_rows, linear_rows, edgeconv, edgeconv_fused_ok, edgeconv_infer, edgeconv_infer_ok,
                      group_mlp_infer, storage_alias, module_cache, EdgeInverseBatch, rows_infer, rows_infer_ok,
-                     cloud_mlp_infer, cloud_mlp_infer_ok)
+                     cloud_mlp_infer, cloud_mlp_infer_ok, point_head_infer, point_head_infer_ok)
 from .replay import active as _replay
 from ._lib import call, ptr, stream_ptr
 
@@ -584,7 +584,8 @@ class PointNetEncoder(nn.Module):
         self.global_feat = global_feat
         self.eval_fuse = False      # fused eval-mode stack + per-cloud max kernel (pcseg.engine.set_eval_fuse)
 
-    def forward_points(self, xp):
+    def _points(self, xp):
+        """xp (B, N, k) -> (g (B, 1024) pooled, r (B*N, 64) point rows, trans, trans_feat)."""
         B, N, _ = xp.shape
         trans = self.stn.forward_points(xp)
         xp = torch.bmm(xp, trans)
@@ -593,17 +594,20 @@ class PointNetEncoder(nn.Module):
         if self.feature_transform:
             trans_feat = self.fstn.forward_points(r.view(B, N, -1))
             r = torch.bmm(r.view(B, N, -1), trans_feat).reshape(B * N, -1)
-        pf = r.view(B, N, -1)
         # conv2 -> BN -> ReLU -> conv3 -> BN (no activation, PointNet.py:82-83) in one engine stack
         convs, bns, acts = [self.conv2, self.conv3], [self.bn2, self.bn3], ('relu', 'none')
         if self.eval_fuse and not torch.is_grad_enabled() and cloud_mlp_infer_ok(convs, bns, 64, acts):
             g = cloud_mlp_infer(r, 64, B, N, convs, bns, acts)
         else:
-            r = shared_mlp(r, 64, convs, bns, acts)
-            g = r.view(B, N, -1).max(dim=1)[0]
+            g = shared_mlp(r, 64, convs, bns, acts).view(B, N, -1).max(dim=1)[0]
+        return g, r, trans, trans_feat
+
+    def forward_points(self, xp):
+        B, N, _ = xp.shape
+        g, r, trans, trans_feat = self._points(xp)
         if self.global_feat:
             return g, trans, trans_feat
-        return torch.cat([g.view(B, 1, 1024).expand(B, N, 1024), pf], dim=2), trans, trans_feat
+        return torch.cat([g.view(B, 1, 1024).expand(B, N, 1024), r.view(B, N, -1)], dim=2), trans, trans_feat
 
     def forward(self, x):
         out, trans, tf = self.forward_points(x.transpose(1, 2))
@@ -626,9 +630,14 @@ class PointNetSeg(nn.Module):
         self.conv3 = nn.Conv1d(256, 128, 1)
         self.bn3 = nn.BatchNorm1d(128)
         self.conv4 = nn.Conv1d(128, part_classes, 1)
+        self.eval_fuse = False      # fused eval-mode head without the concatenation (pcseg.engine.set_eval_fuse)
 
     def forward(self, x):
         B, N, _ = x.shape
+        convs, bns = [self.conv1, self.conv2, self.conv3, self.conv4], [self.bn1, self.bn2, self.bn3]
+        if self.eval_fuse and not torch.is_grad_enabled() and point_head_infer_ok(convs, bns, 1024, 64):
+            g, r, _, _ = self.feat._points(x)
+            return point_head_infer(r, 64, g, B, N, convs, bns, softmax=True).view(B, N, -1)
         feat, _, _ = self.feat.forward_points(x)
         r = feat.reshape(B * N, -1)
         r = shared_mlp(r, r.shape[1], [self.conv1, self.conv2, self.conv3], [self.bn1, self.bn2, self.bn3], 'relu')

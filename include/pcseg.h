@@ -437,6 +437,26 @@ int pcs_rows_infer(const float* X, int ldx, long long M, const pcs_mlp_layer* la
 int pcs_cloud_mlp_infer_workspace(int B, int N, const pcs_mlp_layer* layers, int nl, size_t* bytes);
 int pcs_cloud_mlp_infer(const float* X, int ldx, int kin, int B, int N, const pcs_mlp_layer* layers,
                         int nl, float* out, void* ws, size_t ws_bytes, void* stream);
+/* Eval-mode PointNet segmentation head in one pass (PointNetEncoder's concatenation, PointNet.py:86-90,
+ * and PointNetSeg.forward, PointNet.py:140-149, under model.eval()) without the concatenation: P (B*N
+ * rows of kp point channels, row stride ldp; cloud b = rows b N .. b N + N - 1) and G (B x kg pooled
+ * channels, row stride ldg) stand for the rows [G[b] | P[row]] of kg + kp channels.  layers: nl = 4
+ * records, fields W .. slope; layers[0].cin = kg + kp, W1's columns [0, kg) multiply G -- once per
+ * cloud, in fp32, as a bias c[b] (the workspace, B x 512 floats) -- and columns [kg, kg + kp) multiply
+ * P.  layers[0 .. 2] are relu(BN(conv)) of widths 512, 256, 128 with BatchNorm on its running
+ * statistics folded into the conv on the device (use_batch must be 0, act ReLU, bias nullable);
+ * layers[3] is the classifier, bias only: gamma, beta, run_mean and run_var null, act none, cout =
+ * classes 1 .. 32.  out (B*N x classes, row stride ldo >= classes) = the logits, or with softmax != 0
+ * exp(y) / sum exp(y) per row (computed max-subtracted).  All four layers run on the bf16 matrix pipe
+ * with pcs_rows_infer's split arithmetic; no activation reaches memory.  kg % 4 == 0, >= 4; kp % 4 ==
+ * 0, 4 .. 128; ldp, ldg, ldw % 4 == 0; P, G and every W 16-B aligned.  Z, coef and the gradients are not
+ * read; W and the running statistics are only read.  pcs_point_head_infer_workspace returns the
+ * workspace bytes, or non-zero (with a message) when the head is not covered.  Nothing is allocated;
+ * both launches are deterministic. */
+int pcs_point_head_infer_workspace(int B, int N, int kg, const pcs_mlp_layer* layers, int nl, size_t* bytes);
+int pcs_point_head_infer(const float* P, int ldp, const float* G, int ldg, int kg, int B, int N,
+                         const pcs_mlp_layer* layers, int nl, int softmax, float* out, int ldo,
+                         void* ws, size_t ws_bytes, void* stream);
 /* the current device's wgrad lane stream (null if none could be created) */
 int pcs_wgrad_lane(void** side_stream);
 /* `stream` waits for every weight gradient enqueued on the current device's lane so far */
