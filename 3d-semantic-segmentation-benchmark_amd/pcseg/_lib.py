@@ -100,6 +100,8 @@ SIGNATURES = {
     'pcs_cloud_mlp_infer': [P, I32, I32, I32, I32, ctypes.c_char_p, I32, P, P, ctypes.c_size_t, P],
     'pcs_point_head_infer_workspace': [I32, I32, I32, ctypes.c_char_p, I32, P],
     'pcs_point_head_infer': [P, I32, P, I32, I32, I32, I32, ctypes.c_char_p, I32, I32, P, I32, P, ctypes.c_size_t, P],
+    'pcs_fp_head_infer_workspace': [I32, I32, I32, I32, I32, ctypes.c_char_p, I32, P],
+    'pcs_fp_head_infer': [P, I32, I32, P, I32, P, P, I32, I32, I32, ctypes.c_char_p, I32, P, I32, P, P],
     'pcs_wgrad_lane': [P],
     'pcs_wgrad_lane_join': [P],
     'pcs_geometry_stream': [P],

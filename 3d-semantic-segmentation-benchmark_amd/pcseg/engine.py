@@ -715,9 +715,10 @@ def set_eval_fuse(module: torch.nn.Module, on: bool = True) -> None:
     """Let every MiniPointNet under `module` run its grouped, max-pooled stack through the fused
     eval-mode kernel (group_mlp_infer), and every TNet / PointNetEncoder its stack pooled over the cloud
     (cloud_mlp_infer), and every PointNetSeg its segmentation head -- conv1 .. conv4 and the softmax on the
-    pooled vector and the point rows, without the concatenation (point_head_infer) -- whenever BatchNorm is
-    in eval mode, grad is disabled and the shape is covered (group_mlp_infer_ok, cloud_mlp_infer_ok,
-    point_head_infer_ok).  Off by default: the folded-weight kernels agree with the layered path to fp32
+    pooled vector and the point rows, without the concatenation (point_head_infer) -- and every PointNetpp /
+    PointNetppMSG / PointNeXt its full-resolution tail, fp1 and the classifier (fp_head_infer), whenever
+    BatchNorm is in eval mode, grad is disabled and the shape is covered (group_mlp_infer_ok,
+    cloud_mlp_infer_ok, point_head_infer_ok, fp_head_infer_ok).  Off by default: the folded-weight kernels agree with the layered path to fp32
     rounding, not bitwise."""
     for m in module.modules():
         if hasattr(m, 'eval_fuse'):
@@ -925,6 +926,89 @@ def point_head_infer(p_rows: torch.Tensor, kp: int, g: torch.Tensor, B: int, N: 
     out = _f32((B * N, couts[3]), dev)
     call('pcs_point_head_infer', ptr(p_rows), p_rows.stride(0), ptr(g), g.stride(0), kg, B, N, recs, 4,
          int(bool(softmax)), ptr(out), out.stride(0), ptr(ws), nws, stream_ptr(dev))
+    return out
+
+
+def fp_head_infer_ok(convs, bns, d1: int, d2: int) -> bool:
+    """The fused eval-mode FeaturePropagation + classifier tail (csrc/fp_head_infer.hip) covers 1 .. 4 1x1
+    convs of width 128 on d1 skip (d1 % 4 == 0, 0 .. 32) + d2 = 128 interpolated channels, each with a
+    BatchNorm on its running statistics and a ReLU, then a bias-only classifier of 1 .. 32 classes (convs[-1];
+    pcs_fp_head_infer_workspace, the only holder of these limits)."""
+    if not (2 <= len(convs) == len(bns) + 1):
+        return False
+    for bn in bns:
+        if (bn.training or bn.running_mean is None or bn.running_var is None or bn.weight is None
+                or bn.bias is None):
+            return False
+    widths = tuple(int(c.weight.shape[0]) for c in convs)
+    key = ('fph', int(d1), int(d2), widths)
+    ok = _ws_cache.get(key)
+    if ok is None:      # sizes only: the records carry non-null placeholder pointers
+        recs, cin = [], int(d1) + int(d2)
+        for C in widths[:-1]:
+            recs.append(_REC.pack(16, ld4(cin), cin, C, 0, 16, 16, 16, 16, 0, 0.0, 1e-5, 0, ACT['relu'], 0.0,
+                                  0, 0, 0, 0, 0, 0, 0.0, 0, 0, 0))
+            cin = C
+        recs.append(_head_record(16, ld4(cin), cin, widths[-1], 0))
+        ok = _ws_cache[key] = load().pcs_fp_head_infer_workspace(1, 1, 3, int(d1), int(d2), b''.join(recs), len(recs),
+                                                                 ctypes.byref(ctypes.c_size_t(0))) == 0
+    return ok
+
+
+def fp_head_infer(f1_rows: torch.Tensor | None, d1: int, f2: torch.Tensor, idx: torch.Tensor, dist: torch.Tensor,
+                  B: int, N: int, convs, bns) -> torch.Tensor:
+    """Eval-mode tail of the PointNet++ family outside autograd (FeaturePropagation, common.py:217-243, and the
+    classifier under model.eval()): f1_rows (B*N, ld) with d1 skip channels (None with d1 = 0), f2 (B, M, 128)
+    coarse features, idx / dist (B, N, 3) of the 3-NN -> (B*N, classes) = convs[-1](relu(BN(conv(..relu(BN(
+    conv([f1 | interp(f2)])))..)))) in one pass (pcs_fp_head_infer): neither the concatenation nor any hidden
+    activation is written.  Nothing is saved or updated; under an active pcseg.replay the kernel's own ReLU
+    decisions are recorded, one mask per hidden layer, as the layered stack's are."""
+    if not (f2.is_cuda and idx.is_cuda and dist.is_cuda and (f1_rows is None or f1_rows.is_cuda)):
+        raise RuntimeError('pcseg ops run only on the GPU (no CPU fallback); got a CPU tensor')
+    f2 = f2.detach().float().contiguous()
+    if f2.dim() != 3 or f2.shape[0] != B or idx.shape != (B, N, 3) or dist.shape != (B, N, 3) or B < 1 or N < 1:
+        raise ValueError(f'fp_head_infer: f2 must be ({B}, M, d2) and idx, dist ({B}, {N}, 3)')
+    M, d2 = int(f2.shape[1]), int(f2.shape[2])
+    d1 = int(d1) if f1_rows is not None else 0
+    if not fp_head_infer_ok(convs, bns, d1, d2):
+        raise ValueError('fp_head_infer: needs eval-mode BatchNorm with running statistics on 1 .. 4 layers of width '
+                         '128, a bias-only classifier of 1 .. 32 classes, d1 % 4 == 0 in 0 .. 32 and d2 == 128')
+    if d1:
+        f1_rows = f1_rows.detach()
+        if f1_rows.dim() != 2 or f1_rows.shape[0] != B * N:
+            raise ValueError(f'fp_head_infer: f1_rows must be ({B} * {N}, ld) rows')
+        if f1_rows.dtype != torch.float32 or not _rows_ok(f1_rows) or f1_rows.shape[1] < d1:
+            f1_rows = pad_rows(f1_rows[:, :d1].float())
+    else:
+        f1_rows = None
+    idx = idx.contiguous()
+    if idx.dtype != torch.int32:
+        idx = idx.int()
+    dist = dist.detach().float().contiguous()
+    if f2.data_ptr() % 16:
+        f2 = f2.clone()
+    dev = f2.device
+    params = []
+    for conv, bn in zip(convs, bns):
+        params += [conv.weight, conv.bias, bn.weight, bn.bias]
+    couts = [c.weight.shape[0] for c in convs]
+    nl = len(bns)
+    statics, Wms, _ = _layer_statics(d1 + d2, bns, ((ACT['relu'], 0.0),) * nl, params, couts[:nl], dev)
+    Wc = convs[-1].weight.detach().reshape(couts[-1], -1)
+    if not _rows_ok(Wc):
+        Wc = pad_rows(Wc)
+    Wms.append(Wc)
+    if any(W.data_ptr() % 16 for W in Wms):
+        raise ValueError('fp_head_infer: the weights must be 16-B aligned')
+    recs = b''.join(s + _DYN.pack(0, 0, 0, 0, 0, 0, 0.0, 0, 0, 0) for s in statics)
+    recs += _head_record(Wc.data_ptr(), Wc.stride(0), couts[nl - 1], couts[-1], _nz(convs[-1].bias))
+    out = _f32((B * N, couts[-1]), dev)
+    mask = torch.empty((nl, B * N, couts[0]), dtype=torch.uint8, device=dev) if recording() else None
+    call('pcs_fp_head_infer', ptr(f1_rows), f1_rows.stride(0) if d1 else 0, d1, ptr(f2), d2, ptr(idx), ptr(dist),
+         B, N, M, recs, nl + 1, ptr(out), out.stride(0), ptr(mask), stream_ptr(dev))
+    if mask is not None:
+        for m in mask:
+            record_act_mask(m.bool())
     return out
 
 

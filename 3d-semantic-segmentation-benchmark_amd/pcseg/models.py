@@ -19,7 +19,8 @@ from . import ops
 from .common import SetAbstraction, FeaturePropagation, InvResMLP, UnitPointNet, GeometryPlan, GeometryPrefetch
 from .engine import (shared_mlp, pad_rows, linear_rows, edgeconv, edgeconv_fused_ok, edgeconv_infer, edgeconv_infer_ok,
                      group_mlp_infer, storage_alias, module_cache, EdgeInverseBatch, rows_infer, rows_infer_ok,
-                     cloud_mlp_infer, cloud_mlp_infer_ok, point_head_infer, point_head_infer_ok)
+                     cloud_mlp_infer, cloud_mlp_infer_ok, point_head_infer, point_head_infer_ok, fp_head_infer,
+                     fp_head_infer_ok)
 from .replay import active as _replay
 from ._lib import call, ptr, stream_ptr
 
@@ -47,6 +48,25 @@ def _fused_dropout(drop: nn.Module):
     return None
 
 
+def _fp_tail(model: nn.Module, c0, c1, f0, f1, geo) -> torch.Tensor:
+    """The PointNet++ family's full-resolution tail: fp1 (3-NN interpolation of f1 onto c0, the skip f0 or
+    None, its shared MLP), the head's Dropout and the classifier -> (B*N, classes) rows.  With
+    model.eval_fuse, under eval() + no_grad and a covered shape, one fp_head_infer launch on the plan's
+    3-NN (it takes precedence over eval_gemm for these layers); both paths wait for the geometry stream
+    in geo.fp(0)."""
+    B, N, _ = c0.shape
+    dz = _fused_dropout(model.drop)       # the head's Dropout, fused into FP1's output
+    nn3 = geo.fp(0)
+    if model.eval_fuse and not model.training and dz is None and not torch.is_grad_enabled():
+        convs, bns = [*model.fp1.point_net.conv, model.conv], list(model.fp1.point_net.batch)
+        d1 = 0 if f0 is None else f0.shape[2]
+        if fp_head_infer_ok(convs, bns, d1, f1.shape[2]):
+            return fp_head_infer(None if f0 is None else f0.reshape(B * N, d1), d1, f1, nn3[0], nn3[1], B, N, convs, bns)
+    f = model.fp1(c0, c1, f0, f1, geo=nn3, dropout=dz)
+    gemm = (model.eval_gemm, model.eval_gemm_rows)
+    return _head_rows(f.reshape(B * N, -1), None if dz else model.drop, model.conv, gemm)
+
+
 class PointNetpp(GeometryPrefetch, nn.Module):
     """PointNet++ SSG semantic segmentation (reference PointNetpp.py:6-48)."""
 
@@ -63,6 +83,7 @@ class PointNetpp(GeometryPrefetch, nn.Module):
         self.drop = nn.Dropout(0.5)
         self.conv = nn.Conv1d(128, part_classes, 1)
         self.eval_gemm, self.eval_gemm_rows = 'fp32', 0     # pcseg.engine.set_eval_gemm: the classifier's GEMM
+        self.eval_fuse = False      # fused eval-mode fp1 + classifier tail (pcseg.engine.set_eval_fuse)
 
     def _plan_for(self, c0, inverse=True, into=None):
         return GeometryPlan(c0, [(sa.C, [(sa.radius, sa.K, False)]) for sa in (self.sa1, self.sa2, self.sa3, self.sa4)],
@@ -81,10 +102,7 @@ class PointNetpp(GeometryPrefetch, nn.Module):
         f3 = self.fp4(c3, c4, f3, f4, geo=geo.fp(3))
         f2 = self.fp3(c2, c3, f2, f3, geo=geo.fp(2))
         f1 = self._prefetch_point(self.fp2(c1, c2, f1, f2, geo=geo.fp(1)))
-        dz = _fused_dropout(self.drop)       # the head's Dropout, fused into FP1's output
-        f0 = self.fp1(c0, c1, None, f1, geo=geo.fp(0), dropout=dz)
-        gemm = (self.eval_gemm, self.eval_gemm_rows)
-        return _head_rows(f0.reshape(B * N, -1), None if dz else self.drop, self.conv, gemm).view(B, N, -1)
+        return _fp_tail(self, c0, c1, None, f1, geo).view(B, N, -1)
 
 
 class PointNetppMSG(GeometryPrefetch, nn.Module):
@@ -121,6 +139,7 @@ class PointNetppMSG(GeometryPrefetch, nn.Module):
         self.drop = nn.Dropout(0.5)
         self.conv = nn.Conv1d(128, part_classes, 1)
         self.eval_gemm, self.eval_gemm_rows = 'fp32', 0     # pcseg.engine.set_eval_gemm: the classifier's GEMM
+        self.eval_fuse = False      # fused eval-mode fp1 + classifier tail (pcseg.engine.set_eval_fuse)
 
     def _plan_for(self, c0, inverse=True, into=None):
         return GeometryPlan(c0, [(br[0].C, [(sa.radius, sa.K, False) for sa in br]) for br in self.levels],
@@ -152,10 +171,7 @@ class PointNetppMSG(GeometryPrefetch, nn.Module):
         f3 = self.fp4(cs[3], cs[4], fs[3], fs[4], geo=geo.fp(3))
         f2 = self.fp3(cs[2], cs[3], fs[2], f3, geo=geo.fp(2))
         f1 = self._prefetch_point(self.fp2(cs[1], cs[2], fs[1], f2, geo=geo.fp(1)))
-        dz = _fused_dropout(self.drop)       # the head's Dropout, fused into FP1's output
-        f0 = self.fp1(cs[0], cs[1], None, f1, geo=geo.fp(0), dropout=dz)
-        gemm = (self.eval_gemm, self.eval_gemm_rows)
-        return _head_rows(f0.reshape(B * N, -1), None if dz else self.drop, self.conv, gemm).view(B, N, -1)
+        return _fp_tail(self, cs[0], cs[1], None, f1, geo).view(B, N, -1)
 
 
 class PointNeXt(GeometryPrefetch, nn.Module):
@@ -190,6 +206,7 @@ class PointNeXt(GeometryPrefetch, nn.Module):
         self.drop = nn.Dropout(0.5)
         self.conv = nn.Conv1d(fp1, part_classes, 1)
         self.eval_gemm, self.eval_gemm_rows = 'fp32', 0     # pcseg.engine.set_eval_gemm: the classifier's GEMM
+        self.eval_fuse = False      # fused eval-mode fp1 + classifier tail (pcseg.engine.set_eval_fuse)
 
     def _plan_for(self, c0, inverse=True, into=None):
         def q(m, on_self):
@@ -219,10 +236,7 @@ class PointNeXt(GeometryPrefetch, nn.Module):
         f3 = self.fp4(c3, c4, f3, f4, geo=geo.fp(3))
         f2 = self.fp3(c2, c3, f2, f3, geo=geo.fp(2))
         f1 = self._prefetch_point(self.fp2(c1, c2, f1, f2, geo=geo.fp(1)))
-        dz = _fused_dropout(self.drop)       # the head's Dropout, fused into FP1's output
-        f0 = self.fp1(c0, c1, f0, f1, geo=geo.fp(0), dropout=dz)
-        gemm = (self.eval_gemm, self.eval_gemm_rows)
-        return _head_rows(f0.reshape(B * N, -1), None if dz else self.drop, self.conv, gemm).view(B, N, -1)
+        return _fp_tail(self, c0, c1, f0, f1, geo).view(B, N, -1)
 
 
 # ------------------------------------------------------------------------- DGCNN

@@ -457,6 +457,26 @@ int pcs_point_head_infer_workspace(int B, int N, int kg, const pcs_mlp_layer* la
 int pcs_point_head_infer(const float* P, int ldp, const float* G, int ldg, int kg, int B, int N,
                          const pcs_mlp_layer* layers, int nl, int softmax, float* out, int ldo,
                          void* ws, size_t ws_bytes, void* stream);
+/* Eval-mode full-resolution tail of the PointNet++ family in one pass (FeaturePropagation, common.py:115-122,
+ * 217-243, and the classifier, PointNetpp.py:46-47, under model.eval()): rows [f1[row] | interp(f2[b])[row]]
+ * -- f1 (B*N rows of D1 skip channels, row stride ld1; null with D1 = 0), f2 (B, M, D2 = 128) contiguous,
+ * idx / dist (B, N, 3) of pcs_knn_select, the interpolation in pcs_interp_cat_fwd's per-element fp32
+ * arithmetic -- through nrec - 1 hidden layers relu(BN(conv)) of width 128 (1 .. 4; BatchNorm on its
+ * running statistics folded into the conv on the device; use_batch must be 0, act ReLU, bias nullable) and
+ * the classifier layers[nrec - 1], bias only (gamma, beta, run_mean and run_var null, act none, cout =
+ * classes 1 .. 32).  out (B*N x classes, row stride ldo >= classes) = the logits.  All layers run on the
+ * bf16 matrix pipe with pcs_rows_infer's split arithmetic; neither the concatenation nor any activation
+ * reaches memory.  mask: null, or (nrec - 1, B*N, 128) bytes that receive each hidden layer's ReLU
+ * decisions (pre-activation > 0).  D1 % 4 == 0, 0 .. 32; M >= 3; every idx in [0, M); ld1, ldw % 4 == 0;
+ * f1, f2 and every W 16-B aligned.  Z, coef and the gradients are not read; W and the running statistics
+ * are only read.  pcs_fp_head_infer_workspace takes sizes only, holds every shape limit and returns
+ * non-zero (with a message) when the tail is not covered; the kernel needs no workspace (*bytes = 0).
+ * Nothing is allocated; the launch is deterministic. */
+int pcs_fp_head_infer_workspace(int B, int N, int M, int D1, int D2, const pcs_mlp_layer* layers, int nrec,
+                                size_t* bytes);
+int pcs_fp_head_infer(const float* f1, int ld1, int D1, const float* f2, int D2, const int32_t* idx,
+                      const float* dist, int B, int N, int M, const pcs_mlp_layer* layers, int nrec,
+                      float* out, int ldo, uint8_t* mask, void* stream);
 /* the current device's wgrad lane stream (null if none could be created) */
 int pcs_wgrad_lane(void** side_stream);
 /* `stream` waits for every weight gradient enqueued on the current device's lane so far */
